@@ -12,8 +12,14 @@ sieve.clj:15-34), with every rank's inputs already on its GPU:
 Timing: every step runs from the call to the counts on the
 host; the headline is the median over the K timed steps of the per-step
 maximum over ranks. The K steps are also bracketed by barrier + synchronize
-(ms_per_step_bracketed), and K launches are timed back to back without host
-round trips (ms_per_step_pipelined).
+(ms_per_step_bracketed).
+A plain run does only that: set up, warm up, time the K steps, print the line.
+--full adds what takes work of its own: HIP events around every sieve launch
+(kernel_ms and the roofline), K more launches timed back to back without host
+round trips (ms_per_step_pipelined), the committed PMC figures and the CPU
+baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy
+(dump_outputs below), so that two builds can be compared output for output.
 --window: the high-offset window [1e18, 1e18+1e10] split over the ranks
 (BASELINE config 5): rank 0 builds the base primes <= 1e9 + 4, RCCL
 broadcast, every rank sieves one contiguous slice, RCCL all-reduce.
@@ -60,7 +66,12 @@ def parse():
                     help="sieve limit N (default 1e11, the headline); spell it --N under torch.distributed.run")
     ap.add_argument("--window", action="store_true", help="the [1e18, 1e18+1e10] window instead of [3, N]")
     ap.add_argument("--no-mask", action="store_true", help="count only (not the product path; diagnostics)")
-    ap.add_argument("--cpu-baseline", choices=["on", "off"], default="on")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report what the headline does not need: per-launch kernel times and the "
+                         "roofline, pipelined steps, the committed PMC figures, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's counts and mask figures as DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", choices=["on", "off"], default="on", help="with --full only")
     ap.add_argument("--cpu-max-n", type=float, default=1e8, help="largest N of the CPU baseline runs")
     ap.add_argument("--rccl-single", action="store_true",
                     help="one GPU only: form a 1-rank nccl (RCCL) process group and run the step's broadcast and "
@@ -228,6 +239,67 @@ def lds_instr_check(wm: int, cs: int, pmc):
             "unit": "LDS wave-instructions per launch"}
 
 
+DUMP_BLOCK_WORDS = 4096     # mask words per mask_block_popcount entry (262,144 bits: exact in float32)
+DUMP_SAMPLE_WORDS = 65536   # draws of the seeded mask-word sample (64 float32 each: 16 MB)
+DUMP_SEED = 20240229
+
+
+def _byte_popcounts(x):
+    """int64 tensor -> int64 tensor whose every byte holds that byte's bit count
+    (the arithmetic shifts' sign bits fall outside the masks)."""
+    x = x - ((x >> 1) & 0x5555555555555555)
+    x = (x & 0x3333333333333333) + ((x >> 2) & 0x3333333333333333)
+    return (x + (x >> 4)) & 0x0F0F0F0F0F0F0F0F
+
+
+def dump_outputs(dirname: str, rank: int, world: int, counts_host, mask, nbits: int,
+                 chunk_blocks: int = 4096) -> None:
+    """What a caller of the timed path holds after the last timed step, as
+    float .npy files (well under 64 MB in all):
+      counts.npy               float64 [2]: the counts as they arrived on the
+                               host (chunks, tail; all-reduced over the ranks)
+      mask_block_popcount.npy  float32: prime bits per DUMP_BLOCK_WORDS mask
+                               words, over the whole mask
+      mask_sample_index.npy    float64: the sampled mask words' indices (sorted;
+                               a fixed seed, so the same for the same arguments)
+      mask_sample_bits.npy     float32 [len(index), 64]: bit j of each sampled word
+    Bits of the last word past nbits are not part of the result and read as 0.
+    With more than one rank every rank writes its own mask files (_rank<r>).
+    The mask is reduced on its device, chunk_blocks blocks (128 MB) at a time."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    if rank == 0:
+        np.save(os.path.join(dirname, "counts.npy"), np.asarray(counts_host, dtype=np.float64))
+    if mask is None:
+        return
+    sfx = "" if world == 1 else f"_rank{rank}"
+    words = mask.numel()
+    # the last word's valid bits, as a signed 64-bit constant
+    keep = (1 << (nbits % 64)) - 1 if nbits % 64 else (1 << 64) - 1
+    keep = keep - (1 << 64) if keep >> 63 else keep
+    blocks = []
+    chunk = DUMP_BLOCK_WORDS * chunk_blocks
+    for s in range(0, words, chunk):
+        x = mask[s:s + chunk]
+        if s + chunk >= words:
+            x = x.clone()
+            x[-1] &= keep
+            pad = -x.numel() % DUMP_BLOCK_WORDS
+            if pad:
+                x = torch.cat([x, x.new_zeros(pad)])
+        b = _byte_popcounts(x).view(torch.uint8).view(-1, DUMP_BLOCK_WORDS * 8)
+        blocks.append(b.sum(dim=1, dtype=torch.int64).cpu())
+    np.save(os.path.join(dirname, f"mask_block_popcount{sfx}.npy"), torch.cat(blocks).numpy().astype(np.float32))
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.arange(words) if words <= DUMP_SAMPLE_WORDS else np.unique(rng.integers(0, words, DUMP_SAMPLE_WORDS))
+    w = mask[torch.from_numpy(idx).to(mask.device)].cpu().numpy().view(np.uint64)
+    if idx[-1] == words - 1:
+        w[-1] &= np.uint64(keep & ((1 << 64) - 1))
+    bits = np.unpackbits(w.view(np.uint8).reshape(-1, 8), axis=1, bitorder="little")
+    np.save(os.path.join(dirname, f"mask_sample_index{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, f"mask_sample_bits{sfx}.npy"), bits.astype(np.float32))
+
+
 class Watchdog:
     """A stuck rank must end the run with a diagnosable non-zero exit, not run
     into the driver's time limit: every phase (rendezvous, warmup, timed steps,
@@ -352,12 +424,12 @@ def run(a, world: int, rank: int, wd: Watchdog):
             dist.broadcast(table[:pbytes], src=0)
             if rank != 0:
                 ctx.base_table_finish_dev_async(limit, table.data_ptr(), tbytes, sp)
-        if timed:
+        if timed and a.full:
             e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             e[0].record(stream)
         ctx.sieve_range_dev_async(table.data_ptr(), g0, cs, mask.data_ptr() if mask is not None else 0,
                                   counts.data_ptr(), sp)
-        if timed:
+        if timed and a.full:
             e[1].record(stream)
             kev.append(e)
         if rank == world - 1 and tail_n:
@@ -389,24 +461,30 @@ def run(a, world: int, rank: int, wd: Watchdog):
         step_s.append(dt)
     barrier()
     t1 = time.perf_counter()
-    # back-to-back launches without host round trips (the r01 headline method)
-    wd.phase("pipelined steps")
-    barrier()
-    tp0 = time.perf_counter()
-    for _ in range(a.steps):
-        launch()
-    barrier()
-    tp1 = time.perf_counter()
+    if a.dump_outputs:
+        wd.phase("dump outputs")
+        dump_outputs(a.dump_outputs, rank, world, c, mask, cs)
+    tp0 = tp1 = 0.0
+    if a.full:
+        # back-to-back launches without host round trips (the r01 headline method)
+        wd.phase("pipelined steps")
+        barrier()
+        tp0 = time.perf_counter()
+        for _ in range(a.steps):
+            launch()
+        barrier()
+        tp1 = time.perf_counter()
 
     wd.phase("reduce timings")
     step_t = torch.tensor(step_s + [t1 - t0, tp1 - tp0], dtype=torch.float64, device=dev)
-    kern = sum(e0.elapsed_time(e1) for e0, e1 in kev) / len(kev) / 1e3  # s per sieve launch
+    kern = sum(e0.elapsed_time(e1) for e0, e1 in kev) / len(kev) / 1e3 if a.full else 0.0  # s per sieve launch
     kern_t = torch.tensor([kern], dtype=torch.float64, device=dev)
     # this rank's own figures, next to its device in world.ranks (a SCALE line
     # can then be checked rank by rank against profiles/*/rank_steps.txt)
-    mine = {"step_ms": statistics.median(step_s) * 1e3, "kernel_ms": kern * 1e3,
-            "bracketed_ms": (t1 - t0) / a.steps * 1e3, "pipelined_ms": (tp1 - tp0) / a.steps * 1e3,
+    mine = {"step_ms": statistics.median(step_s) * 1e3, "bracketed_ms": (t1 - t0) / a.steps * 1e3,
             "g_start": g0, "nbits": cs, "tail_nbits": tail_n if rank == world - 1 else 0}
+    if a.full:
+        mine.update({"kernel_ms": kern * 1e3, "pipelined_ms": (tp1 - tp0) / a.steps * 1e3})
     per_rank = [mine]
     if world > 1:
         per_rank = [None] * world
@@ -427,9 +505,13 @@ def run(a, world: int, rank: int, wd: Watchdog):
         verified = KNOWN_PI.get(N) == pi_full if N in KNOWN_PI else None
     if rank == 0:
         ks = kern_t.item()
+        rf = window_roofline = None  # --full only
         if a.window:
             workload = f"window [1e18, 1e18+1e10] split into {P} slice(s), one per GPU (count only, segment-only)"
-            rf = None
+        else:
+            workload = (f"N={N:.0e} odd-only chunked sieve, P={P} spread-work chunks (one per GPU), mask resident "
+                        "in HBM" + (" [count-only diagnostic]" if a.no_mask else ""))
+        if a.window and a.full:
             # the bucketed pass is the window's dominant cost (bucket fill/stage
             # ~57% of a call): HBM-bound on its entries, 4 B written by the fill
             # and read back by the wheel kernel per hit of a prime > 2^19
@@ -452,11 +534,9 @@ def run(a, world: int, rank: int, wd: Watchdog):
                          "in the window (mail_sieve_e/work.py WINDOW_BUCKET_ENTRIES, tools/window_entries.py) against "
                          "8 TB/s HBM",
             }
-        else:
-            workload = (f"N={N:.0e} odd-only chunked sieve, P={P} spread-work chunks (one per GPU), mask resident "
-                        "in HBM" + (" [count-only diagnostic]" if a.no_mask else ""))
+        elif a.full:
             rf = work.roofline(g0, cs, ks)
-        pmc = pmc_summary(N, P, a.window) if with_mask else None
+        pmc = pmc_summary(N, P, a.window) if with_mask and a.full else None
         out = {
             "metric": WINDOW_METRIC if a.window else METRIC,
             "value": N / med,
@@ -476,7 +556,8 @@ def run(a, world: int, rank: int, wd: Watchdog):
                        "parallelism": f"range-partition x{P} (RCCL broadcast + all-reduce)"},
             "timing": "median over steps of the per-step max over ranks, call -> counts on the host",
             "ms_per_step_bracketed": bracketed * 1e3,
-            "ms_per_step_pipelined": pipelined * 1e3,
+            "ms_per_step_pipelined": pipelined * 1e3 if a.full else None,
+            "full": a.full,
             "pi_ref": pi_ref,
             "pi_full": pi_full,
             "verified": verified,
@@ -538,7 +619,7 @@ def run(a, world: int, rank: int, wd: Watchdog):
                     "lds_instr_check": lds_instr_check(wm, cs, pmc),
                 },
             }
-        if world == 1 and a.cpu_baseline == "on" and not a.window:
+        if a.full and world == 1 and a.cpu_baseline == "on" and not a.window:
             wd.phase("cpu baseline")
             out["cpu_baseline"] = cpu_baseline(int(a.cpu_max_n))
         print(json.dumps(out), flush=True)

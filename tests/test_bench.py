@@ -1,7 +1,9 @@
 """bench.py's contract: one JSON line with the BASELINE metric, a roofline and
 cpu_baseline object, and pi verified; the N-rank path (broadcast, all-reduce,
 max-over-ranks timing) rehearsed with 2 ranks on one GPU over gloo
-(DSE_BENCH_REHEARSE=1; the driver's real N-GPU runs use RCCL)."""
+(DSE_BENCH_REHEARSE=1; the driver's real N-GPU runs use RCCL). The roofline,
+kernel times, pipelined steps and cpu_baseline belong to `--full`; a plain run
+prints the headline alone, and `--dump-outputs` writes the last step's results."""
 import json
 import os
 import socket
@@ -51,8 +53,8 @@ def _check_line(d: dict, n_gpus: int):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "1e10", "--steps", "3", "--warmup", "1",
-                        "--cpu-baseline", "on", "--cpu-max-n", "1e7"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "1e10", "--steps", "3",
+                        "--warmup", "1", "--cpu-baseline", "on", "--cpu-max-n", "1e7"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -73,7 +75,7 @@ def test_bench_window_two_rank_rehearsal():
     env = dict(os.environ, DSE_BENCH_REHEARSE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--window", "--steps", "2", "--warmup", "1"],
+                        "--full", "--gpus", "2", "--window", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -91,7 +93,8 @@ def test_bench_window_two_rank_rehearsal():
 def test_bench_window_single_gpu_line():
     """BASELINE config 5 on one GPU: the count verified and an HBM roofline of
     the bucketed pass (8 B per bucket entry, WINDOW_BUCKET_ENTRIES of them)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--window", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--window", "--steps", "3",
+                        "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -111,7 +114,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, DSE_BENCH_REHEARSE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--N", "1e10", "--steps", "2", "--warmup", "1"],
+                        "--full", "--gpus", "2", "--N", "1e10", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -125,14 +128,92 @@ def test_bench_single_rank_rccl_line():
     of the counts run through a real 1-rank nccl (RCCL) process group, formed
     by the same init_process_group("nccl", device_id=...) call an N-GPU rank
     makes; pi stays verified and the line names the nccl backend."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "1e10", "--steps", "3", "--warmup", "1",
-                        "--cpu-baseline", "off", "--rccl-single"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "1e10", "--steps", "3",
+                        "--warmup", "1", "--cpu-baseline", "off", "--rccl-single"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     _check_line(d, 1)
     assert d["world"]["backend"] == "nccl" and d["world"]["rccl_single"] is True
     assert d["pi_full"] == 455052511
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(oracle, tmp_path):
+    """A plain run: --steps sets the timed steps, the line carries the headline
+    and none of the --full figures, and --dump-outputs writes the last step's
+    counts and mask figures, equal to the oracle's chunk. N=1e8: 781,250 mask
+    words (a sampled mask, a partial last popcount block) of which the last
+    holds 63 valid bits."""
+    import numpy as np
+    N = 10**8
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "1e8", "--steps", "4",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["metric"].startswith("sieved integers/sec at N=1e11") and d["unit"] == "integers/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["pi_full"] == 5761455  # pi(1e8)
+    assert d["ms_per_step"] > 0 and abs(d["value"] - N / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["ms_per_step_pipelined"] is None
+    assert all("kernel_ms" not in x and "pipelined_ms" not in x for x in d["world"]["ranks"])
+    out = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(out) == ["counts", "mask_block_popcount", "mask_sample_bits", "mask_sample_index"]
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    cs = (N - 1) // 2
+    words = (cs + 63) // 64
+    m_ref, c_ref = oracle.fast_sieve_range(0, cs)
+    assert cs % 64 == 63 and out["counts"].tolist() == [float(c_ref), 0.0] and c_ref == 5761455 - 1
+    bits = np.unpackbits(np.asarray(m_ref, dtype=np.uint64).view(np.uint8).reshape(-1, 8), axis=1, bitorder="little")
+    bits[-1, cs % 64:] = 0
+    pc = bits.sum(axis=1)
+    want = np.add.reduceat(pc, np.arange(0, words, 4096))
+    assert out["mask_block_popcount"].shape == (-(-words // 4096),)
+    assert np.array_equal(out["mask_block_popcount"], want.astype(np.float32))
+    assert out["mask_block_popcount"].sum(dtype=np.float64) == c_ref
+    idx = out["mask_sample_index"].astype(np.int64)
+    assert 60000 < len(idx) <= 65536 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < words
+    assert out["mask_sample_bits"].shape == (len(idx), 64)
+    assert np.array_equal(out["mask_sample_bits"], bits[idx].astype(np.float32))
+
+
+def test_dump_outputs_matches_numpy(tmp_path):
+    """bench.dump_outputs on a host tensor (CPU only): random 64-bit words, the
+    sign bit included, reduced over several chunks with a partial last block
+    and a partial last word; the sample's indices repeat from call to call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    words = 2 * 3 * 4096 + 1000            # chunks of 2 blocks: 3 full chunks and a partial one
+    w = rng.integers(0, 2**64, words, dtype=np.uint64)
+    w[-1] = np.uint64(2**64 - 1)
+    nbits = 64 * (words - 1) + 5
+    mask = torch.from_numpy(w.view(np.int64).copy())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0, 1, [123, 4], mask, nbits, chunk_blocks=2)
+    assert np.array_equal(mask.numpy().view(np.uint64), w)  # the mask itself is left alone
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) and a[k].dtype == b[k].dtype for k in a)
+    assert a["counts"].dtype == np.float64 and a["counts"].tolist() == [123.0, 4.0]
+    bits = np.unpackbits(w.view(np.uint8).reshape(-1, 8), axis=1, bitorder="little")
+    bits[-1, 5:] = 0
+    want = np.add.reduceat(bits.sum(axis=1), np.arange(0, words, bench.DUMP_BLOCK_WORDS))
+    assert a["mask_block_popcount"].dtype == np.float32 and np.array_equal(a["mask_block_popcount"], want)
+    idx = a["mask_sample_index"].astype(np.int64)
+    assert np.array_equal(idx, np.arange(words))  # fewer words than the sample: all of them
+    assert a["mask_sample_bits"].dtype == np.float32 and np.array_equal(a["mask_sample_bits"], bits)
+    # count-only paths (no mask) write the counts alone; other ranks write no counts
+    bench.dump_outputs(str(tmp_path / "c"), 0, 1, [9, 0], None, 0)
+    assert os.listdir(tmp_path / "c") == ["counts.npy"]
+    bench.dump_outputs(str(tmp_path / "e"), 1, 2, [9, 0], mask, nbits, chunk_blocks=2)
+    assert sorted(os.listdir(tmp_path / "e")) == ["mask_block_popcount_rank1.npy", "mask_sample_bits_rank1.npy",
+                                                  "mask_sample_index_rank1.npy"]
 
 
 def test_watchdog_names_rank_and_phase():

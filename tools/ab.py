@@ -6,7 +6,7 @@ for rnd in range(2):
     for v in variants:
         env = dict(os.environ, **v)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3",
-                            "--cpu-baseline", "off"], env=env, capture_output=True, text=True, timeout=300)
+                            "--full", "--cpu-baseline", "off"], env=env, capture_output=True, text=True, timeout=300)
         if r.returncode:
             print(v, "FAILED", r.stderr[-400:]); sys.exit(1)
         j = json.loads(r.stdout.strip().splitlines()[-1])

@@ -12,7 +12,7 @@ for rnd in range(rounds):
             else os.path.join(ROOT, "variants", f"libdse_{name}.so")
         env = dict(os.environ, DSE_LIB=lib)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3",
-                            "--cpu-baseline", "off", "--n", N] + extra, env=env, capture_output=True, text=True,
+                            "--full", "--cpu-baseline", "off", "--n", N] + extra, env=env, capture_output=True, text=True,
                            timeout=300)
         if r.returncode:
             print(name, "FAILED", r.stderr[-400:], flush=True); sys.exit(1)

@@ -4,7 +4,7 @@
 set -o pipefail
 OUT=${OUT:-gpurun_out/rank_steps}
 mkdir -p $OUT
-timeout -k 10 180 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 180 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python3 -c "import json; j=json.load(open('$OUT/bench.json')); print('bench', j['ms_per_step'], j['value'], j['verified'], j['roofline']['kernel_ms'])"
 timeout -k 10 300 python tools/config_sweep.py $OUT/configs_1gpu.json > $OUT/configs.log 2>&1 || { tail -20 $OUT/configs.log; exit 1; }
 tail -12 $OUT/configs.log

@@ -6,7 +6,7 @@ set -o pipefail
 OUT=${OUT:-gpurun_out/window_ev}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-timeout -k 10 300 python bench.py --window --steps 10 --warmup 3 > $OUT/bench_window.json 2> $OUT/bench_window.err || { tail -20 $OUT/bench_window.err; exit 1; }
+timeout -k 10 300 python bench.py --full --window --steps 10 --warmup 3 > $OUT/bench_window.json 2> $OUT/bench_window.err || { tail -20 $OUT/bench_window.err; exit 1; }
 python3 -c "import json; j=json.load(open('$OUT/bench_window.json')); r=j['roofline']; print('window', j['ms_per_step'], j['verified'], r['kernel_ms'], r['frac'])"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o run -- python3 bench.py --window --steps 5 --warmup 2 > $OUT/kstats.log 2>&1 || { tail -20 $OUT/kstats.log; exit 1; }
 cp "$(find $OUT/kstats -name '*kernel_stats.csv' | head -1)" $OUT/window_kernel_stats.csv

@@ -6,7 +6,7 @@
 # Usage (via gpurun): bash tools/profile.sh <tag> [bench args...]
 set -u
 TAG=${1:-r01}; shift || true
-ARGS=${*:---steps 5 --warmup 2 --cpu-baseline off}
+ARGS=${*:---full --steps 5 --warmup 2 --cpu-baseline off}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT/summary
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
