@@ -1,5 +1,6 @@
-// Internal interface between the gfx950 kernels (dse_base.hip, dse_wheel.hip) and the
-// C-ABI host layer (dse_host.cpp). Not installed; include/dse.h is the ABI.
+// Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
+// dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip) and the C-ABI host layer
+// (dse_host.cpp). Not installed; include/dse.h is the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,10 +38,11 @@ __host__ __device__ inline uint64_t table_bytes_for_cap(uint32_t cap) {
 // The 8 residues mod 30 coprime to 30 (wheel planes, absolute numbering).
 constexpr uint32_t kR30[8] = {1, 7, 11, 13, 17, 19, 23, 29};
 
-// Mod-30 wheel segment geometry (dse_wheel.hip): a segment is 2^17 periods of
-// 30 integers, 8 planes (one per coprime residue) x 8 columns of 2^14 periods
-// (one 128 KiB LDS image). dse_wheel_half.hip compiles the same kernel with
-// 2^16 periods per segment (range tails).
+// Mod-30 wheel segment geometry (dse_wheel_geometry.h): a segment is 2^17
+// periods of 30 integers, 8 planes (one per coprime residue) x 8 columns of
+// 2^14 periods (one 128 KiB LDS image). dse_wheel_half.hip compiles the same
+// kernel (dse_wheel_kernel.h) with 2^16 periods per segment (range tails,
+// DESIGN.md section 4.1.2).
 #ifndef DSE_WHEEL_LOG_KP
 #define DSE_WHEEL_LOG_KP 17
 #endif
@@ -48,10 +50,10 @@ constexpr int kWheelLogKP = DSE_WHEEL_LOG_KP;
 constexpr uint64_t kWheelSpan = 30ull << kWheelLogKP;   // integers per segment
 constexpr uint64_t kWheelOutBits = kWheelSpan / 2;      // odd candidates per segment
 // Ranges with base primes above this go through the bucketed pass
-// (dse_wheel.hip), which then buckets every prime above 2^kBucketLoLog.
+// (dse_bucket.hip), which then buckets every prime above 2^kBucketLoLog.
 #ifndef DSE_WHEEL_MAX_LOG
 // Builds support 19 and 20 only: the L list's table words carry the prime in
-// 20 bits (dse_wheel.hip kLPrimeMask), and the bucket threshold 2^19 must not
+// 20 bits (dse_wheel_kernel.h kLPrimeMask), and the bucket threshold 2^19 must not
 // exceed it. (r05 window A/B: 2^22 7.25 ms, 2^21 6.11, 2^20 5.62, 2^19 5.49)
 #define DSE_WHEEL_MAX_LOG 20
 #endif
@@ -123,14 +125,24 @@ hipError_t launch_sieve_ranges(const void* table, const RangeSpec* rs, size_t n,
 hipError_t launch_sieve_range(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,
                               unsigned long long* count, int num_cus, hipStream_t stream, Scratch* scratch,
                               const SieveOpts* opts);
+// A range whose primes reach above kWheelMaxPrime, as bucketed passes
+// (dse_bucket.hip; launch_sieve_ranges routes such ranges here).
+hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,
+                           unsigned long long* count, int num_cus, hipStream_t stream, Scratch* scratch,
+                           const SieveOpts* opts);
 // The same sieve with the half-size segment geometry (2^16 periods,
 // dse_wheel_half.hip): launch_sieve_ranges gives it the segments past the last
 // full round of a launch when that finishes sooner. No bucketed primes.
 hipError_t launch_wheel_ranges_half(const void* table, const RangeSpec* rs, size_t n, int num_cus,
                                     hipStream_t stream);
-// The full-geometry wheel kernel without bucketed primes (dse_wheel_plain.hip,
-// its own compile flags); wa points at the caller's WheelArgs (dse_wheel.hip).
-hipError_t launch_wheel_plain(const void* table, const void* wa, int num_cus, hipStream_t stream);
+// One persistent launch of the full-geometry wheel kernel over wa (built by
+// make_wheel_args, dse_wheel_geometry.h, in a unit of the full geometry), one
+// per instantiation, each in a unit with its own compile flags: without bucket
+// units (dse_wheel_plain.hip; wa.bk_* unused) and with them (dse_wheel.hip;
+// launch_bucketed's passes, wa.bk_* set).
+struct WheelArgs;
+hipError_t launch_wheel_plain(const void* table, const WheelArgs& wa, int num_cus, hipStream_t stream);
+hipError_t launch_wheel_bucketed(const void* table, const WheelArgs& wa, int num_cus, hipStream_t stream);
 // Fill the Barrett factors m[] and wheel offsets a[] of a table whose p[] is final.
 // n_hint: table capacity when known (sizes the grid: about 4 primes per thread)
 hipError_t launch_wheel_offsets(void* table, int num_cus, hipStream_t stream, uint64_t n_hint = 0);

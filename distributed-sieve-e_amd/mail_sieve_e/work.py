@@ -103,7 +103,7 @@ def bucket_entries_for_range(g_start: int, nbits: int, lo_p: int = BUCKET_LO) ->
     """Bucket entries the bucketed pass writes (and the wheel kernel reads
     back) for the odd-index range: one per multiple p*m in the range with
     gcd(m, 30) = 1 and p*m >= p^2 of every prime lo_p < p <= sqrt(vmax)
-    (csrc/dse_wheel.hip bucket_fill_stage_kernel; the range must reach past
+    (csrc/dse_bucket.hip bucket_fill_stage_kernel; the range must reach past
     2^20, or the wheel kernel takes all its primes itself). Needs the primes up
     to sqrt(vmax): ~0.5 GB and ~10 s of numpy for the 1e18 window
     (tools/window_entries.py keeps that one as WINDOW_BUCKET_ENTRIES)."""

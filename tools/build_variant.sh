@@ -11,6 +11,7 @@ $H -c -o /tmp/dse_var_$NAME/k.o $D/dse_base.hip
 W=${WHEEL_FLAGS-$(sed -n "s/^WHEEL_FLAGS ?= //p" $D/Makefile)}  # the Makefile's wheel flags unless set
 $H $W -c -o /tmp/dse_var_$NAME/w.o $D/dse_wheel.hip
 [ -f $D/dse_wheel_half.hip ] && $H $W -c -o /tmp/dse_var_$NAME/wh.o $D/dse_wheel_half.hip
+[ -f $D/dse_bucket.hip ] && $H $W -c -o /tmp/dse_var_$NAME/wb.o $D/dse_bucket.hip  # (older revisions: part of dse_wheel.hip)
 PL=${PLAIN_FLAGS-$(sed -n "s/^PLAIN_FLAGS ?= *//p" $D/Makefile)}
 [ -f $D/dse_wheel_plain.hip ] && $H $PL -c -o /tmp/dse_var_$NAME/wp.o $D/dse_wheel_plain.hip
 $H -c -o /tmp/dse_var_$NAME/h.o $D/dse_host.cpp

@@ -33,7 +33,7 @@ def main(root):
     for f in os.listdir(SRC):
         if f.endswith((".hip", ".cpp", ".h")) or f == "Makefile":
             shutil.copy(os.path.join(SRC, f), os.path.join(out, f))
-    p = os.path.join(out, "dse_wheel.hip")
+    p = os.path.join(out, "dse_wheel_kernel.h")  # the kernel of all three instantiating units
     s = open(p).read()
     s = sub(s, "namespace dse {\nnamespace {\n",
             "#ifndef DSE_KNOCK\n#define DSE_KNOCK 0\n#endif\nnamespace dse {\nnamespace {\n")

@@ -5,10 +5,11 @@ the shipping sources carry no timing code).
   python tools/instrument_timing.py ROOT
 
 copies distributed-sieve-e_amd/csrc/* (and include/dse.h) under ROOT and inserts s_memtime
-stamps into dse_wheel.hip: per wave, the cycles of mark / mark barrier /
+stamps into dse_wheel_kernel.h: per wave, the cycles of mark / mark barrier /
 expand / init / segment barrier and, with the LDS drained after every unit,
 of the A, B1, B2, L and bucket units, summed into a per-TU __device__ array
-and read by an extra C entry point dse_debug_timing(unsigned long long[16]).
+(one per unit that instantiates the kernel) and read by an extra C entry
+point dse_debug_timing(unsigned long long[96]) added to dse_wheel.hip.
 Then `SRC_DIR=ROOT/distributed-sieve-e_amd/csrc bash tools/build_variant.sh timing` builds
 variants/libdse_timing.so, and tools/wave_timing.py reads it. Draining per
 unit serialises the marking a little, so the unit split is an attribution,
@@ -35,7 +36,7 @@ def main(root):
     for f in os.listdir(SRC):
         if f.endswith((".hip", ".cpp", ".h")) or f == "Makefile":
             shutil.copy(os.path.join(SRC, f), os.path.join(out, f))
-    p = os.path.join(out, "dse_wheel.hip")
+    p = os.path.join(out, "dse_wheel_kernel.h")
     s = open(p).read()
     s = sub(s, "namespace dse {\nnamespace {\n",
             "namespace dse {\nnamespace {\n__device__ unsigned long long g_timing[16];\n"
@@ -73,15 +74,12 @@ def main(root):
             "  if (lane_id == 0)\n    for (int i = 0; i < 10; ++i) atomicAdd(&g_timing[i], (unsigned long long)t_acc[i]);\n"
             "  if (lane_id == 0)\n    for (int i = 0; i < 5; ++i) atomicAdd(&g_timing_w[wave * 5 + i], (unsigned long long)t_acc[i]);\n\n"
             "  if (tid < wa.nranges && lds.rcnt[tid])")
-    s = sub(s, "}  // namespace dse\n", """#if DSE_WHEEL_PLAIN_TU
-int timing_take_plain(unsigned long long* acc) {
-#elif DSE_WHEEL_HALF_TU
-int timing_take_half(unsigned long long* acc) {
-#else
-int timing_take_plain(unsigned long long* acc);
-int timing_take_half(unsigned long long* acc);
-int timing_take_main(unsigned long long* acc) {
-#endif
+    open(p, "w").write(s)
+    # every unit that instantiates the kernel has its own copy of the arrays
+    # (the header's anonymous namespace) and hands it over by its own function
+    for unit, tag in (("dse_wheel.hip", "main"), ("dse_wheel_plain.hip", "plain"), ("dse_wheel_half.hip", "half")):
+        p = os.path.join(out, unit)
+        take = """int timing_take_%s(unsigned long long* acc) {
   unsigned long long t[16], tw[80];
   if (hipMemcpyFromSymbol(t, HIP_SYMBOL(g_timing), sizeof(t)) != hipSuccess) return -1;
   if (hipMemcpyFromSymbol(tw, HIP_SYMBOL(g_timing_w), sizeof(tw)) != hipSuccess) return -1;
@@ -91,17 +89,19 @@ int timing_take_main(unsigned long long* acc) {
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_timing_w), z, sizeof(tw)) != hipSuccess) return -1;
   return hipMemcpyToSymbol(HIP_SYMBOL(g_timing), z, sizeof(t)) == hipSuccess ? 0 : -1;
 }
-#if DSE_WHEEL_MAIN_TU
+""" % tag
+        if tag == "main":
+            take += """int timing_take_plain(unsigned long long* acc);
+int timing_take_half(unsigned long long* acc);
 // out[0..16): phase and unit sums over all waves; out[16 + 5 w + i]: phase i
 // (mark, mark barrier, expand, init, segment barrier) of the waves with id w
 extern "C" int dse_debug_timing(unsigned long long* out) {
   for (int i = 0; i < 96; ++i) out[i] = 0;
   return (timing_take_main(out) || timing_take_plain(out) || timing_take_half(out)) ? -1 : 0;
 }
-#endif
-}  // namespace dse
-""")
-    open(p, "w").write(s)
+"""
+        s = sub(open(p).read(), "}  // namespace dse\n", take + "}  // namespace dse\n")
+        open(p, "w").write(s)
     print(out)
 
 

@@ -21,8 +21,9 @@ def make_var(name):
 
 
 def main(extra):
-    tus = [("dse_wheel.hip", make_var("WHEEL_FLAGS")), ("dse_wheel_half.hip", make_var("WHEEL_FLAGS")),
-           ("dse_wheel_plain.hip", make_var("PLAIN_FLAGS")), ("dse_base.hip", [])]
+    tus = [("dse_wheel.hip", make_var("WHEEL_FLAGS")), ("dse_bucket.hip", make_var("WHEEL_FLAGS")),
+           ("dse_wheel_half.hip", make_var("WHEEL_FLAGS")), ("dse_wheel_plain.hip", make_var("PLAIN_FLAGS")),
+           ("dse_base.hip", [])]
     for tu, fl in tus:
         if not os.path.exists(os.path.join(CSRC, tu)):
             continue
