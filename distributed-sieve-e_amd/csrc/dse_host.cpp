@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/dse.h"
+#include "dse_expand_bits.h"
 #include "dse_internal.h"
 
 namespace {
@@ -781,6 +782,15 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     return DSE_OK;
   }
   return fail(DSE_EINVAL, "unknown stat " + n);
+}
+
+int32_t dse_debug_expand_block(int32_t variant, const uint32_t planes[8], uint32_t out[15]) {
+  if (!planes || !out) return fail(DSE_EINVAL, "null planes or out");
+  uint32_t p[8], o[15];
+  std::memcpy(p, planes, sizeof p);
+  if (!dse::expand_block_variant(variant, p, o)) return fail(DSE_EINVAL, "expand variant outside 0..14");
+  std::memcpy(out, o, sizeof o);
+  return DSE_OK;
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@ WheelRange make_wheel_range(const RangeSpec& rs, uint64_t* plane_lut) {
   w.out = rs.out;
   w.count = rs.count;
   const uint32_t v0m = (uint32_t)(w.V0 % 30);
+  w.variant = v0m / 2;  // V0 is even
   uint32_t n = 0;
   *plane_lut = 0;
   for (uint32_t rho = 1; rho < 30; rho += 2) {

@@ -166,6 +166,7 @@ struct WheelRange {
   // lcap[min(s >> lsh, kLPieces - 1)] (>= the odd primes with p^2 < its end)
   uint32_t lsh;
   uint32_t lcap[kLPieces];
+  uint32_t variant;    // (V0 mod 30) / 2: which slots the planes take in a period (dse_expand_bits.h)
 };
 
 struct WheelArgs {

@@ -19,14 +19,19 @@
 //         walks its plane's hits in order;
 //      L  (p > TB): one prime per lane, its 8 planes in a lane-rotated order,
 //         starts from the table's wheel offsets with one reduction;
-//   2. expand: lane reads one block (two ds_read_b128), transposes the 8x32
-//      bits into 32 period bytes, maps each through a 256-entry LDS table to
-//      the 15 odd slots of its period (composite bits in, prime slots out),
-//      packs 480 output bits, fixes the small primes 3..79, masks the range
-//      end, popcounts, stores; then each wave inits (patterns of 7..61) the
-//      blocks it expanded, for the next segment.
+//   2. expand: lane reads one block (two ds_read_b128) and turns its 8 plane
+//      words (composite bits) into the block's 15 output words (prime bits at
+//      the 15 odd slots of each period) in registers: a 16 x 16 bit transpose
+//      with the planes as rows at their slots, then a rotate and masked ORs
+//      per register (dse_expand_bits.h; one static body per V0 mod 30, chosen
+//      once per segment); fixes the small primes 3..79, masks the range end,
+//      popcounts, stores; then each wave inits (patterns of 7..79) the blocks
+//      it expanded, for the next segment.
 // See DESIGN.md section 4 for the rooflines.
 #pragma once
+#include <type_traits>
+
+#include "dse_expand_bits.h"
 #include "dse_wheel_geometry.h"
 
 namespace dse {
@@ -324,35 +329,6 @@ __device__ __forceinline__ uint32_t first_at_or_after(uint32_t kp, uint32_t star
 // Smallest plane index k whose value Vs + rho + 30k is >= p^2, given D = p^2 - Vs > 0.
 __device__ __forceinline__ uint32_t kmin_for(uint32_t D, uint32_t rho) {
   return D > rho ? (D - rho + 29u) / 30u : 0u;
-}
-
-// (x & m) | (y & ~m): v_bfi_b32
-// (the compiler rewrites the C form into v_and + v_bitop3 pairs)
-__device__ __forceinline__ uint32_t bfi(uint32_t m, uint32_t x, uint32_t y) {
-  uint32_t r;
-  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(m), "v"(x), "v"(y));
-  return r;
-}
-
-// Transpose the 8 x 8 bit matrix in each byte column q of W[0..7] (row i =
-// W[i] byte q): afterwards W[j] byte q bit i = old W[i] byte q bit j. Three
-// rounds of block swaps between rows i and i + s (blocks of s bits), 4 VALU
-// per swap: the upper s bits of row i's blocks trade places with the lower s
-// bits of row i + s's.
-template <int S>
-__device__ __forceinline__ void bit_block_swap(uint32_t& a, uint32_t& b) {
-  constexpr uint32_t m = S == 4 ? 0x0F0F0F0Fu : S == 2 ? 0x33333333u : 0x55555555u;
-  const uint32_t x = a, y = b;
-  b = bfi(m, x >> S, y);
-  a = bfi(~m, y << S, x);
-}
-__device__ __forceinline__ void bit_block_swaps(uint32_t (&W)[8]) {
-  bit_block_swap<4>(W[0], W[4]); bit_block_swap<4>(W[1], W[5]);
-  bit_block_swap<4>(W[2], W[6]); bit_block_swap<4>(W[3], W[7]);
-  bit_block_swap<2>(W[0], W[2]); bit_block_swap<2>(W[1], W[3]);
-  bit_block_swap<2>(W[4], W[6]); bit_block_swap<2>(W[5], W[7]);
-  bit_block_swap<1>(W[0], W[1]); bit_block_swap<1>(W[2], W[3]);
-  bit_block_swap<1>(W[4], W[5]); bit_block_swap<1>(W[6], W[7]);
 }
 
 // ---- work units of the mark phase ----------------------------------------
@@ -816,7 +792,6 @@ struct WheelLdsLow {
   uint32_t mid_x[kMidCap];         // Vs mod p of this workgroup's segment (MidRes)
   uint32_t mid_inc[kMidCap];       // G W mod p
   uint32_t x_seg;                  // the launch segment mid_x holds (~0: none)
-  uint32_t lut[kMaxRanges][256];   // per range: period byte -> 15 odd slots
   uint4 itab[kGDW];                // init tables U_G, 4 copies shifted by 0..3 dwords (kGDW / 4 blocks each)
   uint32_t thr[5];
   uint32_t ctr;                    // unit counter
@@ -874,19 +849,6 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     lds.x_seg = ~0u;
   }
   if (tid < kMaxRanges) lds.rcnt[tid] = 0;
-  for (uint32_t x = tid; x < 256 * wa.nranges; x += NT) {
-    const uint32_t v8 = x & 255;
-    const uint64_t rho_pack = wa.r[x >> 8].rho_pack;
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 8; ++i) {
-      const uint32_t rho = (uint32_t)(rho_pack >> (5 * i)) & 31u;
-      if (!(v8 & (1u << i))) v |= 1u << ((rho - 1) >> 1);  // plane bit i clear: prime
-    }
-    // composite bits of the 8 planes -> prime odd slots of the period, filed
-    // under v ^ 3 (v >> 5) (see expand_segment)
-    lds.lut[x >> 8][v8 ^ (3u * (v8 >> 5))] = v;
-  }
   for (uint32_t idx = tid; idx < 4 * kGDW; idx += NT) reinterpret_cast<uint32_t*>(lds.itab)[idx] = g_init_tables.w[idx];
   __syncthreads();
   const uint32_t i_mid0 = s_thr[0], i_midB = s_thr[1], i_midB2 = s_thr[2], i_mid1 = s_thr[3];
@@ -1011,13 +973,14 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
   // put the halves back: 1e11 +0.4%, profiles/r05/ab_expand_reads.txt).
   // Output words 15 R .. 15 R + 14 of block R: a wave stores 3,840
   // contiguous bytes per step.
-  auto expand_segment = [&](const uint32_t* __restrict__ img, uint32_t g_seg) {
-    const uint32_t ri = range_of(g_seg);
+  // The block loop for the range's variant VT (the slots its planes take in
+  // a period, dse_expand_bits.h): one static body per variant.
+  auto expand_blocks = [&](const uint32_t* __restrict__ img, uint32_t g_seg, uint32_t ri, auto vt) {
+    constexpr int VT = decltype(vt)::value;
     const WheelRange& rg = wa.r[ri];
     const uint64_t s = g_seg - rg.seg0;  // the range's segment
     const uint64_t out_words = 2ull * ((rg.nbits + 63) / 64);  // 32-bit words of the caller's mask
     uint32_t* __restrict__ out = rg.out;
-    const uint32_t* __restrict__ s_lut = lds.lut[ri];
     uint32_t my_count = 0;
     uint32_t lane = lane_id;
     asm volatile("" : "+v"(lane));
@@ -1026,6 +989,7 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     const uint32_t m = l < 4 ? l : l < 12 ? l - 4 : l < 20 ? l - 8 : l < 28 ? l - 12 : l - 16;
     const uint32_t bl = 16 * (2 * (lane >> 5) + gsub) + m;  // block within the step
     const uint64_t seg_word0 = s * (uint64_t)kOutWordsPerSeg;
+    const ExpandMasks masks = expand_masks();  // in SGPRs for this segment's blocks only
 #pragma unroll 1
     for (uint32_t t = 0; t < kExpandBlocks / 64; ++t) {
       const uint32_t blk = kExpandBlocks * wave + 64 * t + bl;
@@ -1033,36 +997,16 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
       const uint4 lo = rp[0], hi = rp[1];
       uint32_t W[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};  // composite bits of planes 0..7
       // composite candidates of the block's 256 (8 planes x 32 periods), from
-      // the raw words (the transpose keeps it): 8 v_bcnt instead of 15 over
-      // the output words; the range's first block (small primes put back by
-      // rg.fix) and its end count the output instead
+      // the raw words: 8 v_bcnt instead of 15 over the output words; the
+      // range's first block (small primes put back by rg.fix) and its end
+      // count the output instead
       uint32_t n_comp = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) n_comp += __popc(W[j]);
-      // Transpose every byte column of the 8 x 32 bit matrix in place (rows =
-      // planes): afterwards W[j] byte q bit i = plane i, period 8q + j.
-      bit_block_swaps(W);
-      // LUT index of every period byte v: v ^ 3 (v >> 5), a bijection that
-      // puts the common bytes (all composite, one prime) in distinct banks
-      // (indexed by v, 255 / 223 / 191 / 127 would share bank 31)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t h = (W[j] >> 5) & 0x07070707u;
-        W[j] ^= h + (h << 1);  // 3h <= 21: no carry into the next byte
-      }
+      // composite bits of 8 planes x 32 periods -> prime bits of 32 periods x
+      // 15 odd slots, in registers
       uint32_t o[15];
-#pragma unroll
-      for (int w = 0; w < 15; ++w) o[w] = 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const uint32_t e = s_lut[(W[j] >> (8 * q)) & 0xFFu];
-          const int pos = 15 * (8 * q + j);
-          o[pos >> 5] |= e << (pos & 31);
-          if ((pos & 31) > 17) o[(pos >> 5) + 1] |= e >> (32 - (pos & 31));
-        }
-      }
+      expand_block<VT>(W, o, masks);
       const uint64_t w0 = seg_word0 + 15ull * blk;  // caller's 32-bit word index
       if (s == 0 && blk == 0) {
         o[0] |= (uint32_t)rg.fix;
@@ -1102,6 +1046,19 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) my_count += __shfl_xor(my_count, o);
     if (lane == 0 && my_count) atomicAdd(&lds.rcnt[ri], (unsigned long long)my_count);
+  };
+  // one scalar branch per segment, around the block loop
+  auto expand_segment = [&](const uint32_t* __restrict__ img, uint32_t g_seg) {
+    const uint32_t ri = range_of(g_seg);
+    switch (__builtin_amdgcn_readfirstlane(wa.r[ri].variant)) {
+#define DSE_EXPAND_CASE(V) \
+  case V: expand_blocks(img, g_seg, ri, std::integral_constant<int, V>{}); break;
+      DSE_EXPAND_CASE(0) DSE_EXPAND_CASE(1) DSE_EXPAND_CASE(2) DSE_EXPAND_CASE(3) DSE_EXPAND_CASE(4)
+      DSE_EXPAND_CASE(5) DSE_EXPAND_CASE(6) DSE_EXPAND_CASE(7) DSE_EXPAND_CASE(8) DSE_EXPAND_CASE(9)
+      DSE_EXPAND_CASE(10) DSE_EXPAND_CASE(11) DSE_EXPAND_CASE(12) DSE_EXPAND_CASE(13) DSE_EXPAND_CASE(14)
+#undef DSE_EXPAND_CASE
+      default: break;  // make_wheel_range sets 0..14
+    }
   };
 
   // ---- mark segment s into image img -------------------------------------

@@ -58,6 +58,7 @@ SIGNATURES = {
     "dse_debug_set_option": (_i32, [_vp, _cp, _i64]),
     "dse_debug_init_logical": (_vp, [_i32]),
     "dse_debug_get_stat": (_i32, [_vp, _cp, _pi64]),
+    "dse_debug_expand_block": (_i32, [_i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 _lib = None

@@ -245,6 +245,15 @@ int32_t dse_debug_get_stat(dse_ctx *ctx, const char *name, int64_t *value);
  * failure (dse_last_status). */
 dse_ctx *dse_debug_init_logical(int32_t num_logical);
 
+/* The wheel kernel's block transform of its expand phase, run on the host
+ * (no device call): planes[i] = plane i's word of one image block (bit k set:
+ * the candidate of period k is composite), variant = (V0 mod 30) / 2 of the
+ * range. Writes the block's 15 output words: bit 15k + slot_i is set exactly
+ * when bit k of planes[i] is clear, slot_i being the i-th smallest of
+ * ((r - 1)/2 - variant) mod 15 over the residues r coprime to 30. Test-only;
+ * DSE_EINVAL for a variant outside 0..14 or a null pointer. */
+int32_t dse_debug_expand_block(int32_t variant, const uint32_t planes[8], uint32_t out[15]);
+
 #ifdef __cplusplus
 }
 #endif
