@@ -6,7 +6,9 @@
 //   per-prime [mi ps p] relay through the
 //     lead (sieve.clj:139, core.clj:118-134) -> one RCCL broadcast of base primes
 //   (no result gather in the reference)      -> RCCL all-reduce of counts
-//   finish (sieve.clj:82-108)                -> dse_write_primes_file
+//   finish (sieve.clj:82-108)                -> dse_write_primes_file (host), or
+//                                               dse_finish_resident_file / dse_finish_range_file
+//                                               (text formatted on the device, dse_finish.hip)
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -18,6 +20,7 @@
 
 #include "../../include/dse.h"
 #include "dse_expand_bits.h"
+#include "dse_finish_fmt.h"
 #include "dse_internal.h"
 
 namespace {
@@ -66,6 +69,28 @@ struct ChunkMask {
   uint64_t words = 0;
 };
 
+// Device finish (dse_finish.hip): the tile-sum scratch of the three launches,
+// ordered across streams like dse::Scratch (`done` recorded after the emit
+// launch; the next call's stream waits on it, a grow synchronises on it), and
+// the slab pipeline of the file entry points: two device and two pinned host
+// text buffers of `buf_bytes` each (at most kFinishBufMax), grown on demand.
+constexpr uint64_t kFinishBufMax = 64ull << 20;  // 4 buffers: 256 MiB per device in all
+constexpr uint64_t kFinishBufMin = 1ull << 20;
+struct FinishState {
+  void* sums = nullptr;
+  uint64_t sums_bytes = 0;
+  hipEvent_t done = nullptr;
+  bool used = false;
+  char* dtext[2] = {nullptr, nullptr};
+  char* htext[2] = {nullptr, nullptr};
+  uint64_t buf_bytes = 0;
+  unsigned long long* dtotals = nullptr;  // device [2][2]
+  unsigned long long* htotals = nullptr;  // pinned [2][2]
+  hipStream_t copy = nullptr;             // the text's D2H copies
+  hipEvent_t fmt_ev[2] = {nullptr, nullptr};
+  hipEvent_t copy_ev[2] = {nullptr, nullptr};
+};
+
 struct DevState {
   int device = 0;
   int num_cus = 0;
@@ -78,6 +103,7 @@ struct DevState {
   uint64_t scratch_words = 0;
   std::vector<ChunkMask> resident;       // masks kept by dse_sieve_all
   dse::Scratch scratch;                  // bucketed-pass scratch (high-offset ranges)
+  FinishState fin;                       // device finish: scratch and slab buffers
   hipEvent_t xev = nullptr;              // logical devices: this device's side of a collective
 };
 
@@ -89,6 +115,7 @@ struct dse_ctx {
   int64_t last_n = -1;
   int32_t last_P = 0;
   dse::SieveOpts opts;  // test-only knobs (dse_debug_set_option)
+  uint64_t finish_slab_words = 0;  // test-only: > 0 caps a finish slab at that many mask words
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:
   bool logical = false;
@@ -166,6 +193,23 @@ int32_t free_resident(DevState& d) {
     if (c.dev_ptr) HIP_TRY(hipFree(c.dev_ptr));
   d.resident.clear();
   return DSE_OK;
+}
+
+void free_finish(FinishState& f) {
+  if (f.used && f.done) (void)hipEventSynchronize(f.done);
+  if (f.copy) (void)hipStreamSynchronize(f.copy);
+  if (f.sums) (void)hipFree(f.sums);
+  for (int i = 0; i < 2; ++i) {
+    if (f.dtext[i]) (void)hipFree(f.dtext[i]);
+    if (f.htext[i]) (void)hipHostFree(f.htext[i]);
+    if (f.fmt_ev[i]) (void)hipEventDestroy(f.fmt_ev[i]);
+    if (f.copy_ev[i]) (void)hipEventDestroy(f.copy_ev[i]);
+  }
+  if (f.dtotals) (void)hipFree(f.dtotals);
+  if (f.htotals) (void)hipHostFree(f.htotals);
+  if (f.done) (void)hipEventDestroy(f.done);
+  if (f.copy) (void)hipStreamDestroy(f.copy);
+  f = FinishState();
 }
 
 int32_t chunk_geometry(int64_t n, int32_t P, int64_t* cs) {
@@ -366,6 +410,7 @@ void dse_destroy(dse_ctx* ctx) {
     if (d.counts) (void)hipFree(d.counts);
     if (d.scratch_mask) (void)hipFree(d.scratch_mask);
     (void)dse::free_scratch(&d.scratch);
+    free_finish(d.fin);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }
@@ -479,14 +524,16 @@ int32_t dse_sieve_range_dev_async(dse_ctx* ctx, const void* table_dev, uint64_t 
 }
 
 namespace {
+// keep_dev: sieve into d.scratch_mask even without a host mask (dse_finish_range_file)
 int32_t sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t nbits, uint64_t* mask_or_null,
-                         uint64_t* count) {
+                         uint64_t* count, bool keep_dev = false) {
   int32_t rc;
   HIP_TRY(hipSetDevice(d.device));
   const uint64_t words = (nbits + 63) / 64;
   if ((rc = build_table(d, dse_base_limit_for_range(g0, nbits)))) return rc;
   if ((rc = ensure_counts(d, 1))) return rc;
-  if (mask_or_null && d.scratch_words < words) {
+  const bool dev_mask = mask_or_null || keep_dev;
+  if (dev_mask && d.scratch_words < words) {
     if (d.scratch_mask) HIP_TRY(hipFree(d.scratch_mask));
     d.scratch_mask = nullptr;
     d.scratch_words = 0;
@@ -495,7 +542,7 @@ int32_t sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t nbits,
   }
   HIP_TRY(hipMemsetAsync(d.counts, 0, sizeof(unsigned long long), d.stream));
   HIP_TRY(dse::launch_sieve_range(d.table, g0, nbits,
-                                  mask_or_null ? reinterpret_cast<uint32_t*>(d.scratch_mask) : nullptr,
+                                  dev_mask ? reinterpret_cast<uint32_t*>(d.scratch_mask) : nullptr,
                                   d.counts, d.num_cus, d.stream, &d.scratch, &ctx->opts));
   unsigned long long c = 0;
   HIP_TRY(hipMemcpyAsync(&c, d.counts, sizeof(c), hipMemcpyDeviceToHost, d.stream));
@@ -752,6 +799,11 @@ int32_t dse_debug_set_option(dse_ctx* ctx, const char* name, int64_t value) {
     ctx->opts.table_bcast_max = (uint64_t)value;
     return DSE_OK;
   }
+  if (n == "finish_slab_words") {
+    if (value < 0) return fail(DSE_EINVAL, "finish_slab_words must be >= 0");
+    ctx->finish_slab_words = (uint64_t)value;
+    return DSE_OK;
+  }
   if (n == "bucket_cap_divisor") {
     if (value < 0 || value > 0xFFFFFFFFll) return fail(DSE_EINVAL, "bucket_cap_divisor out of range");
     ctx->opts.bucket_cap_div = (uint32_t)value;
@@ -791,6 +843,12 @@ int32_t dse_debug_expand_block(int32_t variant, const uint32_t planes[8], uint32
   if (!dse::expand_block_variant(variant, p, o)) return fail(DSE_EINVAL, "expand variant outside 0..14");
   std::memcpy(out, o, sizeof o);
   return DSE_OK;
+}
+
+int32_t dse_debug_finish_format(uint64_t v, uint32_t flags, char out[32]) {
+  if (!out) return fail(DSE_EINVAL, "null out");
+  if (flags & ~DSE_FINISH_DOUBLES) return fail(DSE_EINVAL, "only DSE_FINISH_DOUBLES applies to one value");
+  return (int32_t)dse::fin_format_value(v, flags & DSE_FINISH_DOUBLES, 0u, [&](uint32_t p, char c) { out[p] = c; });
 }
 
 }  // extern "C"
@@ -895,4 +953,245 @@ extern "C" int32_t dse_write_primes_file(const char* path, int32_t my_num, int64
   if (my_num < 1 || my_num > P) return fail(DSE_EINVAL, "my_num outside 1..P");
   if (cs < 4) return fail(DSE_EINVAL, "finish's 2/3/5/7 hack needs a chunk of >= 4 candidates");
   return dse_write_range_file(path, my_num, (uint64_t)(my_num - 1) * (uint64_t)cs, (uint64_t)cs, mask);
+}
+
+// ---------------------------------------------------------------------------
+// finish on the device (dse_finish.hip): the mask stays in HBM, text comes back
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kFinishFlagsAll = DSE_FINISH_DOUBLES | DSE_FINISH_HACK | DSE_FINISH_LAST;
+
+// what both the async entry point and the file entry points refuse
+int32_t finish_check_range(uint32_t flags, uint64_t g_start, uint64_t nbits) {
+  if (flags & ~kFinishFlagsAll) return fail(DSE_EINVAL, "unknown finish flag");
+  if ((flags & DSE_FINISH_HACK) && nbits < 4)
+    return fail(DSE_EINVAL, "finish's 2/3/5/7 hack needs a chunk of >= 4 candidates");
+  if (g_start > (1ull << 62) || nbits > (1ull << 62) - g_start)
+    return fail(DSE_ERANGE, "odd-index range beyond 2^62");
+  if ((flags & DSE_FINISH_DOUBLES) && nbits && 3 + 2 * (g_start + nbits - 1) >= (1ull << 53))
+    return fail(DSE_ERANGE, "Double printing needs every value below 2^53");
+  if (nbits > (1ull << 44)) return fail(DSE_ERANGE, "finish range above 2^44 candidates in one call");
+  return DSE_OK;
+}
+
+// The three launches on `stream`, with the context's tile-sum scratch ordered
+// against whatever stream used it last.
+int32_t finish_launch(DevState& d, uint32_t flags, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
+                      uint64_t first_rank, void* text_dev, uint64_t text_cap, unsigned long long* totals_dev,
+                      hipStream_t stream) {
+  FinishState& f = d.fin;
+  if (!f.done) HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+  const uint64_t need = dse::finish_scratch_bytes(nbits);
+  if (f.sums_bytes < need) {
+    if (f.used) HIP_TRY(hipEventSynchronize(f.done));
+    if (f.sums) HIP_TRY(hipFree(f.sums));
+    f.sums = nullptr;
+    f.sums_bytes = 0;
+    f.used = false;
+    const uint64_t want = std::max<uint64_t>(need + need / 2, 1ull << 16);
+    HIP_TRY(hipMalloc(&f.sums, want));
+    f.sums_bytes = want;
+  }
+  if (f.used) HIP_TRY(hipStreamWaitEvent(stream, f.done, 0));
+  HIP_TRY(dse::launch_finish_text(flags, g_start, nbits, mask_dev, first_rank, text_dev, text_cap, totals_dev,
+                                  f.sums, stream));
+  HIP_TRY(hipEventRecord(f.done, stream));
+  f.used = true;
+  return DSE_OK;
+}
+
+int32_t ensure_finish_bufs(DevState& d, uint64_t want) {
+  FinishState& f = d.fin;
+  if (!f.copy) HIP_TRY(hipStreamCreateWithFlags(&f.copy, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    if (!f.fmt_ev[i]) HIP_TRY(hipEventCreateWithFlags(&f.fmt_ev[i], hipEventDisableTiming));
+    if (!f.copy_ev[i]) HIP_TRY(hipEventCreateWithFlags(&f.copy_ev[i], hipEventDisableTiming));
+  }
+  if (!f.dtotals) HIP_TRY(hipMalloc(&f.dtotals, 4 * sizeof(unsigned long long)));
+  if (!f.htotals) HIP_TRY(hipHostMalloc(&f.htotals, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+  want = std::min(std::max(want, kFinishBufMin), kFinishBufMax);
+  if (f.buf_bytes >= want) return DSE_OK;
+  // every earlier call has drained both streams before it returned
+  for (int i = 0; i < 2; ++i) {
+    if (f.dtext[i]) HIP_TRY(hipFree(f.dtext[i]));
+    if (f.htext[i]) HIP_TRY(hipHostFree(f.htext[i]));
+    f.dtext[i] = f.htext[i] = nullptr;
+  }
+  f.buf_bytes = 0;
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(hipMalloc(&f.dtext[i], want));
+    HIP_TRY(hipHostMalloc(&f.htext[i], want, hipHostMallocDefault));
+  }
+  f.buf_bytes = want;
+  return DSE_OK;
+}
+
+// The slab pipeline: mask_dev (ready in d.stream's order) -> file. Slab i+1 is
+// formatted on d.stream while slab i's text is copied on the copy stream and
+// slab i-1 is written to the file by this thread. The rank of a slab's first
+// entry is the sum of the entry counts before it, so a slab is launched once
+// the totals of the one before it are on the host.
+int32_t finish_pipeline(dse_ctx* ctx, DevState& d, FILE* fp, const char* path, uint32_t flags, uint64_t g_start,
+                        uint64_t nbits, const uint64_t* mask_dev, uint64_t* count_out) {
+  const uint64_t words = (nbits + 63) / 64;
+  if (count_out) *count_out = 0;
+  if (!words) return DSE_OK;  // no entries: an empty file
+  int32_t rc;
+  if ((rc = ensure_finish_bufs(d, dse_finish_text_bound(g_start, nbits, nbits, flags)))) return rc;
+  FinishState& f = d.fin;
+  const uint64_t B = f.buf_bytes;
+  const uint64_t cap_words = ctx->finish_slab_words ? ctx->finish_slab_words : ~0ull;
+  uint64_t rank = 0;
+  bool copy_pending[2] = {false, false};
+
+  auto launch = [&](int slot, uint64_t w0, uint64_t nw) -> int32_t {
+    uint32_t fl = flags & DSE_FINISH_DOUBLES;
+    if (w0 == 0) fl |= flags & DSE_FINISH_HACK;
+    if (w0 + nw == words) fl |= DSE_FINISH_LAST;
+    const uint64_t nb = std::min<uint64_t>(nbits - w0 * 64, nw * 64);
+    // the slot's device buffer is free once the copy of the slab that used it has run
+    if (copy_pending[slot]) HIP_TRY(hipStreamWaitEvent(d.stream, f.copy_ev[slot], 0));
+    int32_t r = finish_launch(d, fl, g_start + w0 * 64, nb, mask_dev + w0, rank, f.dtext[slot], B,
+                              f.dtotals + 2 * slot, d.stream);
+    if (r) return r;
+    HIP_TRY(hipMemcpyAsync(f.htotals + 2 * slot, f.dtotals + 2 * slot, 2 * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipEventRecord(f.fmt_ev[slot], d.stream));
+    return DSE_OK;
+  };
+  auto run = [&]() -> int32_t {
+    int32_t r;
+    int slot = 0, prev_slot = -1;
+    uint64_t w0 = 0, prev_bytes = 0;
+    // first guess: 128 text bytes per mask word (a prime mask prints 70..110); later slabs
+    // are sized from the slab before them, and one that does not fit is halved and redone
+    uint64_t nw = std::min(std::min(words, cap_words), std::max<uint64_t>(B / 128, 1));
+    if ((r = launch(slot, w0, nw))) return r;
+    for (;;) {
+      HIP_TRY(hipEventSynchronize(f.fmt_ev[slot]));
+      const uint64_t cnt = f.htotals[2 * slot], bytes = f.htotals[2 * slot + 1];
+      if (bytes > B) {  // nothing was written: split the slab and format it again
+        if (nw == 1) return fail(DSE_EINTERNAL, "finish: one mask word exceeds the text buffer");
+        nw /= 2;
+        if ((r = launch(slot, w0, nw))) return r;
+        continue;
+      }
+      HIP_TRY(hipStreamWaitEvent(f.copy, f.fmt_ev[slot], 0));
+      if (bytes) HIP_TRY(hipMemcpyAsync(f.htext[slot], f.dtext[slot], bytes, hipMemcpyDeviceToHost, f.copy));
+      HIP_TRY(hipEventRecord(f.copy_ev[slot], f.copy));
+      copy_pending[slot] = true;
+      rank += cnt;
+      const uint64_t w_next = w0 + nw;
+      const bool more = w_next < words;
+      uint64_t nw_next = 0;
+      if (more) {
+        const uint64_t per_word = bytes / nw + 1;
+        nw_next = std::max<uint64_t>((B - B / 8) / per_word, 1);
+        nw_next = std::min(std::min(nw_next, words - w_next), cap_words);
+        if ((r = launch(slot ^ 1, w_next, nw_next))) return r;
+      }
+      if (prev_slot >= 0) {
+        HIP_TRY(hipEventSynchronize(f.copy_ev[prev_slot]));
+        if (prev_bytes && std::fwrite(f.htext[prev_slot], 1, prev_bytes, fp) != prev_bytes)
+          return fail(DSE_EIO, std::string("write failed: ") + path);
+      }
+      prev_slot = slot;
+      prev_bytes = bytes;
+      if (!more) break;
+      slot ^= 1;
+      w0 = w_next;
+      nw = nw_next;
+    }
+    HIP_TRY(hipEventSynchronize(f.copy_ev[prev_slot]));
+    if (prev_bytes && std::fwrite(f.htext[prev_slot], 1, prev_bytes, fp) != prev_bytes)
+      return fail(DSE_EIO, std::string("write failed: ") + path);
+    return DSE_OK;
+  };
+  rc = run();
+  if (rc) {  // leave nothing in flight on the buffers
+    (void)hipStreamSynchronize(d.stream);
+    (void)hipStreamSynchronize(f.copy);
+    return rc;
+  }
+  if (count_out) *count_out = rank - ((flags & DSE_FINISH_HACK) ? 4 : 0);
+  return DSE_OK;
+}
+
+uint32_t finish_flags_for(int32_t my_num) {
+  return my_num == 1 ? (DSE_FINISH_DOUBLES | DSE_FINISH_HACK) : 0u;
+}
+
+int32_t finish_close(FILE* fp, const char* path, int32_t rc) {
+  if (std::fclose(fp) != 0 && !rc) return fail(DSE_EIO, std::string("write failed: ") + path);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" uint64_t dse_finish_text_bound(uint64_t g_start, uint64_t nbits, uint64_t count, uint32_t flags) {
+  // every entry: ", " and a value no longer than the range's largest (the
+  // printed length is monotone in the value; the hack literals are shorter
+  // still); a "\n" after every tenth entry wherever the first rank falls, and
+  // the closing one
+  const uint64_t vmax = 3 + 2 * (g_start + (nbits ? nbits - 1 : 0));
+  const uint64_t per = dse::fin_value_len(vmax, flags & DSE_FINISH_DOUBLES) + 2;
+  if (count > (~0ull - 16) / (per + 1)) return ~0ull;
+  return count * per + (count + 9) / 10 + 1;
+}
+
+extern "C" int32_t dse_finish_text_dev_async(dse_ctx* ctx, uint32_t flags, uint64_t g_start, uint64_t nbits,
+                                             const uint64_t* mask_dev, uint64_t first_rank, void* text_dev,
+                                             uint64_t text_cap, uint64_t* totals_dev, void* stream) {
+  if (!ctx || !totals_dev) return fail(DSE_EINVAL, "null ctx or totals");
+  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
+  if (text_cap && !text_dev) return fail(DSE_EINVAL, "null text buffer with a non-zero capacity");
+  int32_t rc = finish_check_range(flags, g_start, nbits);
+  if (rc) return rc;
+  if (first_rank > (1ull << 62)) return fail(DSE_ERANGE, "first_rank beyond 2^62");
+  DevState& d = ctx->devs[0];
+  HIP_TRY(hipSetDevice(d.device));
+  return finish_launch(d, flags, g_start, nbits, mask_dev, first_rank, text_dev, text_cap,
+                       reinterpret_cast<unsigned long long*>(totals_dev), (hipStream_t)stream);
+}
+
+extern "C" int32_t dse_finish_resident_file(dse_ctx* ctx, const char* path, int32_t my_num) {
+  if (!ctx || !path) return fail(DSE_EINVAL, "null ctx or path");
+  if (my_num < 1) return fail(DSE_EINVAL, "my_num must be >= 1");
+  for (auto& d : ctx->devs)
+    for (auto& cm : d.resident)
+      if (cm.my_num == my_num) {
+        int64_t cs;
+        int32_t rc = chunk_geometry(ctx->last_n, ctx->last_P, &cs);
+        if (rc) return rc;
+        const uint32_t flags = finish_flags_for(my_num);
+        const uint64_t g_start = (uint64_t)(my_num - 1) * (uint64_t)cs;
+        if ((rc = finish_check_range(flags, g_start, (uint64_t)cs))) return rc;
+        FILE* fp = std::fopen(path, "wb");
+        if (!fp) return fail(DSE_EIO, std::string("cannot open ") + path);
+        if (hipSetDevice(d.device) != hipSuccess) return finish_close(fp, path, fail(DSE_EHIP, "hipSetDevice failed"));
+        rc = finish_pipeline(ctx, d, fp, path, flags, g_start, (uint64_t)cs, cm.dev_ptr, nullptr);
+        return finish_close(fp, path, rc);
+      }
+  return fail(DSE_EINVAL, "chunk " + std::to_string(my_num) + " is not resident");
+}
+
+extern "C" int32_t dse_finish_range_file(dse_ctx* ctx, const char* path, int32_t my_num, uint64_t g_start,
+                                         uint64_t nbits, uint64_t* count) {
+  if (!ctx || !path) return fail(DSE_EINVAL, "null ctx or path");
+  if (my_num < 1) return fail(DSE_EINVAL, "my_num must be >= 1");
+  const uint32_t flags = finish_flags_for(my_num);
+  int32_t rc = finish_check_range(flags, g_start, nbits);
+  if (rc) return rc;
+  FILE* fp = std::fopen(path, "wb");
+  if (!fp) return fail(DSE_EIO, std::string("cannot open ") + path);
+  DevState& d = ctx->devs[0];
+  uint64_t c = 0;
+  if (nbits) {
+    rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, &c, true);
+    if (!rc) rc = finish_pipeline(ctx, d, fp, path, flags, g_start, nbits, d.scratch_mask, nullptr);
+  }
+  rc = finish_close(fp, path, rc);
+  if (!rc && count) *count = c;
+  return rc;
 }

@@ -147,4 +147,14 @@ hipError_t launch_wheel_bucketed(const void* table, const WheelArgs& wa, int num
 // n_hint: table capacity when known (sizes the grid: about 4 primes per thread)
 hipError_t launch_wheel_offsets(void* table, int num_cus, hipStream_t stream, uint64_t n_hint = 0);
 
+// Device finish (dse_finish.hip): the set bits of mask (odd indices [g_start,
+// g_start + nbits), 64-bit words) as the slice of a primes{k}.txt file whose
+// first entry has rank first_rank; flags = DSE_FINISH_*. totals[0] = entries,
+// totals[1] = text bytes; text is written only when they fit text_cap.
+// tile_sums: finish_scratch_bytes(nbits) bytes of device scratch.
+uint64_t finish_scratch_bytes(uint64_t nbits);
+hipError_t launch_finish_text(uint32_t flags, uint64_t g_start, uint64_t nbits, const uint64_t* mask,
+                              uint64_t first_rank, void* text, uint64_t text_cap, unsigned long long* totals,
+                              void* tile_sums, hipStream_t stream);
+
 }  // namespace dse

@@ -55,6 +55,11 @@ SIGNATURES = {
     "dse_base_table_finish_dev_async": (_i32, [_vp, _u64, _vp, _u64, _vp]),
     "dse_sieve_range_dev_async": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "dse_device_status": (_i32, [_vp]),
+    "dse_finish_text_bound": (_u64, [_u64, _u64, _u64, ctypes.c_uint32]),
+    "dse_finish_text_dev_async": (_i32, [_vp, ctypes.c_uint32, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "dse_finish_resident_file": (_i32, [_vp, _cp, _i32]),
+    "dse_finish_range_file": (_i32, [_vp, _cp, _i32, _u64, _u64, _pu64]),
+    "dse_debug_finish_format": (_i32, [_u64, ctypes.c_uint32, ctypes.c_char_p]),
     "dse_debug_set_option": (_i32, [_vp, _cp, _i64]),
     "dse_debug_init_logical": (_vp, [_i32]),
     "dse_debug_get_stat": (_i32, [_vp, _cp, _pi64]),

@@ -134,6 +134,28 @@ class Context:
                                               count_ptr, stream_ptr or None),
               "dse_sieve_range_dev_async")
 
+    # -- finish on the device -------------------------------------------------
+    def finish_text_dev_async(self, flags: int, g_start: int, nbits: int, mask_ptr: int, first_rank: int,
+                              text_ptr: int, text_cap: int, totals_ptr: int, stream_ptr: int = 0):
+        """The device mask's entries as file text in device memory (include/dse.h
+        dse_finish_text_dev_async): totals[0] = entries, totals[1] = bytes needed."""
+        check(lib().dse_finish_text_dev_async(self.ptr, flags, g_start, nbits, mask_ptr or None, first_rank,
+                                              text_ptr or None, text_cap, totals_ptr, stream_ptr or None),
+              "dse_finish_text_dev_async")
+
+    def finish_resident(self, path: str, my_num: int) -> str:
+        """finish for a chunk the last sieve_all left on its device: the file's
+        text is formatted on the GPU, the mask never reaches the host."""
+        check(lib().dse_finish_resident_file(self.ptr, os.fsencode(path), my_num), "dse_finish_resident_file")
+        return path
+
+    def finish_range(self, path: str, my_num: int, g_start: int, nbits: int) -> int:
+        """gen-table + sieve-e + finish of an odd-index range on the device -> its prime count."""
+        cnt = ctypes.c_uint64()
+        check(lib().dse_finish_range_file(self.ptr, os.fsencode(path), my_num, g_start, nbits, ctypes.byref(cnt)),
+              "dse_finish_range_file")
+        return cnt.value
+
 
 def base_table_bytes(limit: int) -> int:
     return int(lib().dse_base_table_bytes(limit))
@@ -154,6 +176,15 @@ def base_table_broadcast_bytes(limit: int) -> int:
 
 def base_limit_for_range(g_start: int, nbits: int) -> int:
     return int(lib().dse_base_limit_for_range(g_start, nbits))
+
+
+# include/dse.h DSE_FINISH_*
+FINISH_DOUBLES, FINISH_HACK, FINISH_LAST = 1, 2, 4
+
+
+def finish_text_bound(g_start: int, nbits: int, count: int, flags: int = 0) -> int:
+    """Rigorous upper bound on the text bytes of ``count`` entries of the range."""
+    return int(lib().dse_finish_text_bound(g_start, nbits, count, flags))
 
 
 _default_ctx: Optional[Context] = None
@@ -238,19 +269,27 @@ def finish(raw_chunk: Chunk, my_num: int, *, path: Optional[str] = None) -> str:
 
 
 def sieve_e(my_num: int, lead: bool, in_channel, chunk: Chunk, out_channel, *,
-            ctx: Optional[Context] = None, write_file: bool = True, path: Optional[str] = None) -> Chunk:
+            ctx: Optional[Context] = None, write_file: bool = True, path: Optional[str] = None,
+            gpu_finish: bool = False) -> Chunk:
     """sieve.clj:118-172: sieve this machine's chunk, then finish it.
 
     The reference marks the chunk prime by prime, receiving earlier chunks'
     primes on ``in_channel`` and reporting its own on ``out_channel``. Here the
     chunk is sieved in one pass on a GPU with the base primes <= sqrt(upper)
     computed on the device, so the channels carry nothing; they are accepted
-    for call compatibility. ``lead`` likewise no longer orders the work."""
+    for call compatibility. ``lead`` likewise no longer orders the work.
+
+    ``gpu_finish``: write the file with Context.finish_range (the text is
+    formatted on the device) instead of the host writer; same bytes."""
     del lead, in_channel, out_channel
     ctx = ctx or default_context()
     if chunk.cs < 1:
         raise ValueError("empty chunk (find-first-prime would throw)")
     chunk.mask, chunk.n_primes = ctx.sieve_odd_range(chunk.g_start, chunk.cs, want_mask=True)
-    if write_file:
+    if write_file and gpu_finish:
+        if path is None:
+            path = os.path.join(os.path.expanduser("~"), f"primes{my_num}.txt")
+        ctx.finish_range(path, my_num, chunk.g_start, chunk.cs)
+    elif write_file:
         finish(chunk, my_num, path=path)
     return chunk

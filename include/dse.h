@@ -187,6 +187,40 @@ int32_t dse_sieve_range_dev_async(dse_ctx *ctx, const void *table_dev, uint64_t 
  * check overflowed. The blocking entry points check it themselves. */
 int32_t dse_device_status(dse_ctx *ctx);
 
+/* ---- finish on the device ---------------------------------------------- */
+
+/* sieve.clj:82-108 finish with the mask staying in device memory: the mask is
+ * turned into the file's text on the GPU (same bytes as dse_write_range_file)
+ * and only text crosses to the host. */
+#define DSE_FINISH_DOUBLES 1u  /* Double.toString printing (chunk 1) */
+#define DSE_FINISH_HACK    2u  /* ranks 0..3 are 2 3 5 7, bits 0..3 ignored; needs nbits >= 4 */
+#define DSE_FINISH_LAST    4u  /* this slice ends the file: close a partial last line */
+
+/* Rigorous upper bound on the text bytes of `count` entries of the range (host arithmetic only). */
+uint64_t dse_finish_text_bound(uint64_t g_start, uint64_t nbits, uint64_t count, uint32_t flags);
+
+/* Format the set bits of mask_dev (range [g_start, g_start+nbits)) as the slice of a finish file
+ * whose first entry has rank first_rank. totals_dev[0] = entries, totals_dev[1] = text bytes
+ * needed (always written). Text is written to text_dev only if it fits text_cap; otherwise not one
+ * byte of text_dev is touched. Asynchronous on stream. Bits past nbits in the last word are
+ * ignored. With DSE_FINISH_HACK the slice's first four entries are 2 3 5 7. DSE_ERANGE for a range
+ * beyond 2^62, more than 2^44 candidates in one call, or DSE_FINISH_DOUBLES with a value >= 2^53. */
+int32_t dse_finish_text_dev_async(dse_ctx *ctx, uint32_t flags, uint64_t g_start, uint64_t nbits,
+                                  const uint64_t *mask_dev, uint64_t first_rank,
+                                  void *text_dev, uint64_t text_cap, uint64_t *totals_dev, void *stream);
+
+/* finish for chunk my_num kept resident by the last dse_sieve_all: same bytes as
+ * dse_copy_chunk_mask + dse_write_primes_file, without the mask leaving the device. The text is
+ * formatted in slabs of whole mask words through two device and two pinned host buffers (256 MiB
+ * per device in all, kept until dse_destroy): a slab is formatted while the one before it is
+ * copied to the host and the one before that is written to the file. */
+int32_t dse_finish_resident_file(dse_ctx *ctx, const char *path, int32_t my_num);
+
+/* gen-table + sieve-e + finish for an odd-index range with no host mask:
+ * same bytes as dse_sieve_odd_range + dse_write_range_file; *count may be NULL. */
+int32_t dse_finish_range_file(dse_ctx *ctx, const char *path, int32_t my_num,
+                              uint64_t g_start, uint64_t nbits, uint64_t *count);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -221,6 +255,8 @@ int32_t dse_device_status(dse_ctx *ctx);
  *   the primes and ncclAllReduce of the counts as an 8-GPU context instead of
  *   skipping them (the RCCL path exercised on a one-GPU box); 0 = default (no
  *   communicator, no collective for one device).
+ *   "finish_slab_words" = k > 0: dse_finish_resident_file / dse_finish_range_file
+ *   format slabs of at most k mask words (slab seams on tiny inputs); 0 = default.
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -253,6 +289,13 @@ dse_ctx *dse_debug_init_logical(int32_t num_logical);
  * ((r - 1)/2 - variant) mod 15 over the residues r coprime to 30. Test-only;
  * DSE_EINVAL for a variant outside 0..14 or a null pointer. */
 int32_t dse_debug_expand_block(int32_t variant, const uint32_t planes[8], uint32_t out[15]);
+
+/* The finish kernels' own per-value formatter, run on the host (no device
+ * call): prints v into out as a Long, or with DSE_FINISH_DOUBLES as
+ * Double.toString prints it (v < 2^53), and returns the length (no
+ * terminator; at most 24 bytes). Test-only; DSE_EINVAL (negative) for a null
+ * pointer or a flag other than DSE_FINISH_DOUBLES. */
+int32_t dse_debug_finish_format(uint64_t v, uint32_t flags, char out[32]);
 
 #ifdef __cplusplus
 }
