@@ -22,6 +22,17 @@
  *  - Mask layout: little-endian uint64 words, bit j of chunk k = 1 iff the
  *    value 3+2((k-1)cs+j) is prime (= element j non-zero before finish);
  *    bits past cs in the last word are 0.
+ *  - Supported range: every value 3+2g of a sieved range must be below 2^62,
+ *    i.e. the range's last odd index is at most 2^61 - 2 (value 2^62 - 1), so
+ *    that the base primes stop at 2^31 - 1 (dse_base_limit_max). Two checks
+ *    enforce it, both DSE_ERANGE: the entry points that take an odd-index range
+ *    first refuse g_start + nbits > 2^62 (a bound on the INDEX, which keeps
+ *    3+2g inside 64 bits; it alone would admit values up to 2^63), then any
+ *    range whose largest value is 2^62 + 1 or more is refused because it needs
+ *    a base-prime limit of 2^31 or more (dse_sieve_odd_range, dse_sieve_chunk,
+ *    dse_sieve_all, dse_sieve_window, dse_finish_range_file,
+ *    dse_base_primes_dev_async). dse_sieve_range_dev_async checks only the
+ *    index bound: its caller's table fixes the limit.
  */
 #ifndef DSE_H
 #define DSE_H

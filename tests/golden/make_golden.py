@@ -156,6 +156,51 @@ def window(g: dict) -> None:
     print(f"window [1e18, 1e18+1e10]: {c} ({time.time() - t:.1f}s)", flush=True)
 
 
+def prime_values_hash(limit: int, piece_words: int = 1 << 22):
+    """Count, last value and SHA-256 (of the little-endian uint32 values, in
+    order) of the odd primes <= limit < 2^32: fast_sieve_range(0, nbits), then
+    the set bits, then the values 3 + 2 g, hashed piece by piece."""
+    nbits = (limit - 3) // 2 + 1
+    m, c = o.fast_sieve_range(0, nbits)
+    h = hashlib.sha256()
+    n, last = 0, 0
+    for w0 in range(0, len(m), piece_words):
+        bits = np.unpackbits(m[w0:w0 + piece_words].view(np.uint8), bitorder="little")
+        g = np.flatnonzero(bits) + 64 * w0
+        if len(g):
+            v = (3 + 2 * g).astype("<u4")
+            h.update(v.tobytes())
+            n += len(v)
+            last = int(v[-1])
+    assert n == int(c)
+    return n, last, h.hexdigest()
+
+
+TOP_SEG_BITS = 1_966_080                      # odd candidates per wheel segment
+TOP_NB = 5 * TOP_SEG_BITS + 777               # tests/test_gpu_top_of_range.py, several segments at the top
+TOP_G0 = 2**61 - 1 - TOP_NB                   # last index 2^61 - 2: value 2^62 - 1
+
+
+def top(g: dict) -> None:
+    """The top of the accepted range: the base table's primes up to 1e9 and up
+    to 2^31 - 1 (count, last, hash of the values), and the mask of the last
+    5 segments + 777 candidates below 2^62."""
+    res = {}
+    for name, limit in (("primes_1e9", 10**9), ("primes_2p31m1", 2**31 - 1)):
+        t = time.time()
+        n, last, hx = prime_values_hash(limit)
+        res[name] = {"limit": limit, "count": n, "last": last, "values_sha256": hx,
+                     "source": "fast_sieve_range(0, nbits) -> set bits -> uint32 LE values"}
+        print(f"{name}: {n} odd primes, last {last} ({time.time() - t:.1f}s)", flush=True)
+    t = time.time()
+    m, c = o.fast_sieve_range(TOP_G0, TOP_NB)
+    res["segments"] = {"g0": TOP_G0, "nb": TOP_NB, "count": int(c), "mask_sha256": sha(m),
+                       "source": "fast_sieve_range (base primes to 2^31 - 1), window (2a) checked against "
+                                 "Miller-Rabin in tests/test_oracle.py"}
+    print(f"top segments: {int(c)} primes ({time.time() - t:.1f}s)", flush=True)
+    g["top"] = res
+
+
 def main():
     """Default: regenerate the small fixtures (sweep, files, 1e9). Flags add or
     refresh sections of the existing golden.json in place:
@@ -163,9 +208,10 @@ def main():
       --ref1e10  check the 1e10 entries with the faithful restatement
       --big11    1e11 P=1/2/4/8 (streamed)
       --big12    1e12 P=8 (streamed, ~10 min on 8 cores)
-      --window   the [1e18, 1e18+1e10] count"""
+      --window   the [1e18, 1e18+1e10] count
+      --top      base-table primes to 1e9 and 2^31 - 1, and the last segments below 2^62"""
     flags = set(sys.argv[1:])
-    incremental = flags & {"--ref1e10", "--big11", "--big12", "--window"}
+    incremental = flags & {"--ref1e10", "--big11", "--big12", "--window", "--top"}
     if incremental and os.path.exists(OUT):
         g = json.load(open(OUT))
     else:
@@ -179,6 +225,8 @@ def main():
         g["big"].update(big_streamed(10**12, (8,)))
     if "--window" in flags:
         window(g)
+    if "--top" in flags:
+        top(g)
     with open(OUT, "w") as f:
         json.dump(g, f, indent=1)
     print("wrote", OUT)

@@ -147,3 +147,48 @@ def test_product_path_has_no_oracle_dependency():
                 assert "oracle" not in re.sub(r"#.*|//.*", "", txt).replace("no oracle", ""), f
     from mail_sieve_e import _dse
     assert b"liboracle" not in open(_dse.LIB_PATH, "rb").read()
+
+
+# largest prime <= T and smallest prime > T of every prime-class threshold
+# (tests/test_gpu_prime_classes.py), and the table's last two primes
+_THRESHOLD_PRIMES = [131_071, 131_101, 262_139, 262_147, 524_287, 524_309, 1_048_573, 1_048_583, 2_457_569,
+                     2_457_607, 268_435_399, 268_435_459, 503_316_469, 503_316_511, 999_999_937, 1_000_000_007,
+                     2_147_483_629, 2_147_483_647]
+
+
+def test_base_limit_is_the_exact_integer_root():
+    """dse_base_limit_for_range == math.isqrt(vmax) where a rounded root would
+    admit or lose a prime: q^2 - 2, q^2, q^2 + 2 for every threshold prime,
+    2^40 +- 1, 2^62 +- 1 (the first limit past the table), and seeded random
+    values below 2^62."""
+    import math
+    import random
+    from mail_sieve_e import sieve as S
+    vs = [q * q + d for q in _THRESHOLD_PRIMES for d in (-2, 0, 2)]
+    vs += [2**40 - 1, 2**40 + 1, 2**62 - 1, 2**62 + 1]
+    rng = random.Random(0x15A7)
+    vs += [rng.randrange(3, 2**62) | 1 for _ in range(1000)]
+    for v in vs:
+        assert v & 1
+        g = (v - 3) // 2
+        for g0, nb in ((g, 1), (max(0, g - 999), min(g + 1, 1000))):  # vmax = v either way
+            assert S.base_limit_for_range(g0, nb) == math.isqrt(v), v
+    assert S.base_limit_for_range((2**62 - 1 - 3) // 2, 1) == 2**31 - 1
+    assert S.base_limit_for_range((2**62 + 1 - 3) // 2, 1) == 2**31
+
+
+def test_largest_table_holds_every_prime_below_2p31():
+    """The table for limit 2^31 - 1 (kBigBaseLimitMax): capacity for its
+    105,097,564 odd primes, sizes consistent with the layout (header + p[],
+    then 8 B of m[], 32 B of a[] and 8 B of pl[] per slot)."""
+    from mail_sieve_e import _dse
+    from mail_sieve_e import sieve as S
+    lim = 2**31 - 1
+    assert _dse.lib().dse_base_limit_max() == lim
+    pb, tb = S.base_table_prime_bytes(lim), S.base_table_bytes(lim)
+    cap = (pb - 16) // 4
+    assert pb == 16 + 4 * cap and 105_097_564 <= cap < 2**32
+    m_off = (16 + 4 * cap + 7) & ~7
+    a_off = (m_off + 8 * cap + 31) & ~31
+    assert tb == a_off + 32 * cap + 8 * cap
+    assert tb >= 16 + 52 * 105_097_564

@@ -224,29 +224,7 @@ def test_core_lead_single_machine_gpu(tmp_path, oracle):
 
 # ---- high-offset window (outside the reference's semantics) ----
 
-def _is_prime_mr(n):
-    """Deterministic Miller-Rabin for n < 3.3e24 (first 12 prime bases)."""
-    if n < 2:
-        return False
-    bases = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37)
-    for p in bases:
-        if n % p == 0:
-            return n == p
-    d, s = n - 1, 0
-    while d % 2 == 0:
-        d //= 2
-        s += 1
-    for a in bases:
-        x = pow(a, d, n)
-        if x in (1, n - 1):
-            continue
-        for _ in range(s - 1):
-            x = x * x % n
-            if x == n - 1:
-                break
-        else:
-            return False
-    return True
+from primes_ref import is_prime_mr as _is_prime_mr  # noqa: E402  (deterministic Miller-Rabin, n < 3.3e24)
 
 
 def test_big_base_table(ctx):
@@ -342,12 +320,14 @@ def _odd_primes_upto(n):
 
 
 @pytest.mark.parametrize("limit", [3, 4, 9, 10, 97, 1_000, 316_227, 1_000_003, 1_048_577, 1_048_579, 2_097_153,
-                                   2_097_155, 2_457_601])
+                                   2_097_155, 2_457_601, 2_457_603, 2_457_607, 2_457_609, 5_000_011, 16_777_259])
 def test_base_table_primes_exact(ctx, limit):
     """The base table's p[] is every odd prime <= limit, in order, from a
     single odd value up to the largest one-level build (kBaseLimitMax =
     2,457,601; round 6 measured a one-workgroup build of these tables, 79 us
-    against 34 us at 1e11, and dropped it)."""
+    against 34 us at 1e11, and dropped it), then the first two-level builds
+    (2,457,603; 2,457,607 admits that prime; 2,457,609), 5,000,011 and
+    16,777,259 (the first prime above 2^24)."""
     import torch
     from mail_sieve_e import sieve as S
     t = torch.zeros(S.base_table_bytes(limit), dtype=torch.uint8, device="cuda")

@@ -182,3 +182,31 @@ def test_golden_streamed_headline_entries():
     if g is not None:
         assert g["pi_ref"] == 37_607_912_017 and g["pi_full"] == 37_607_912_018
     assert GOLDEN["big"]["window_1e18"]["count"] == 241_272_176
+
+
+@pytest.mark.slow
+def test_fast_sieve_at_the_top_vs_miller_rabin(oracle):
+    """fast_sieve_range generates the golden data at the top of the range
+    (GOLDEN["top"], base primes to 2^31 - 1): on the 2^16 candidates centred
+    on (2^31 - 1)^2 it equals deterministic Miller-Rabin bit for bit (2,990
+    primes; the square's own bit is 0). About 20 s: it sieves the base primes
+    to 2^31 on one thread."""
+    from primes_ref import mask_bits, mr_window
+    M = 2**31 - 1
+    g0, nb = (M * M - 3) // 2 - 2**15, 2**16
+    ref = mr_window(g0, nb)
+    m, c = oracle.fast_sieve_range(g0, nb)
+    bits = mask_bits(m, nb)
+    assert np.array_equal(bits, ref)
+    assert c == int(ref.sum()) == 2990 and not bits[2**15]
+
+
+def test_golden_top_entries():
+    """GOLDEN["top"] (make_golden.py --top): shape and the published counts
+    pi(1e9) - 1 and pi(2^31 - 1) - 1 of odd primes."""
+    top = GOLDEN["top"]
+    assert top["primes_1e9"]["count"] == 50_847_534 - 1 and top["primes_1e9"]["last"] == 999_999_937
+    assert top["primes_2p31m1"]["count"] == 105_097_565 - 1 and top["primes_2p31m1"]["last"] == 2**31 - 1
+    s = top["segments"]
+    assert s["nb"] == 5 * 1_966_080 + 777 and 3 + 2 * (s["g0"] + s["nb"] - 1) == 2**62 - 1
+    assert all("source" in e for e in top.values())
