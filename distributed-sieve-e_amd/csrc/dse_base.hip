@@ -202,7 +202,7 @@ hipError_t launch_sum_rows(const unsigned long long* in, uint32_t nsrc, uint32_t
   return hipGetLastError();
 }
 
-hipError_t launch_base_primes(uint64_t limit, void* table, uint32_t cap, hipStream_t stream) {
+static hipError_t launch_base_primes(uint64_t limit, void* table, uint32_t cap, hipStream_t stream) {
   if (limit > kBaseLimitMax) return hipErrorInvalidValue;
   if (limit < 3) {  // no odd primes: empty table
     TableHeader h{0, cap, limit};
@@ -239,12 +239,7 @@ hipError_t launch_base_primes_big(uint64_t limit, void* table, uint32_t cap, int
   const uint64_t nb = (limit - 3) / 2 + 1;            // odd values 3..limit
   const uint64_t words = (nb + 63) / 64;
   uint64_t* mask = reinterpret_cast<uint64_t*>(mreg);
-  const uint64_t lim0 = [&] {                          // isqrt(limit)
-    uint64_t r = (uint64_t)__builtin_sqrt((double)limit);
-    while (r * r > limit) --r;
-    while ((r + 1) * (r + 1) <= limit) ++r;
-    return r;
-  }();
+  const uint64_t lim0 = isqrt64(limit);
   const uint32_t cap0 = (uint32_t)(1.26 * (double)lim0 / __builtin_log((double)(lim0 > 100 ? lim0 : 100))) + 64;
   char* t0 = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(mreg) + words * 8 + 255) & ~(uintptr_t)255);
   const uint64_t t0_bytes = (table_bytes_for_cap(cap0) + 255) & ~255ull;

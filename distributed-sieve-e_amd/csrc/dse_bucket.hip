@@ -698,53 +698,21 @@ uint32_t bucket_k0(uint32_t i_lo, double a, double b) {
 constexpr uint64_t kBucketMaxEntries = 1ull << 31;  // 8 GB of band-1 entries per pass
 constexpr uint64_t kBucketMaxRegionBytes = 24ull << 30;  // band-0 regions per pass
 
-// Grow the context's scratch to `bytes` for a pass on `stream`, ordered after
-// the previous pass whatever stream that ran on: a grow waits for it on the
-// host (the old buffer is freed), otherwise `stream` waits for its event.
+// The context's scratch at `bytes` for a pass on `stream` (acquire_scratch:
+// ordered after the previous pass whatever stream that ran on), with its
+// overflow flag, created and zeroed on first use.
 hipError_t ensure_scratch(Scratch* sc, uint64_t bytes, hipStream_t stream, char** out) {
   hipError_t e;
-  if (!sc->done && (e = hipEventCreateWithFlags(&sc->done, hipEventDisableTiming)) != hipSuccess) return e;
   if (!sc->flag) {
     if ((e = hipMalloc(&sc->flag, 2 * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = hipMemsetAsync(sc->flag, 0, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;
   }
-  if (sc->bytes < bytes) {
-    if (sc->used && (e = hipEventSynchronize(sc->done)) != hipSuccess) return e;
-    if (sc->ptr && (e = hipFree(sc->ptr)) != hipSuccess) return e;
-    sc->ptr = nullptr;
-    sc->bytes = 0;
-    sc->used = false;
-    if ((e = hipMalloc(&sc->ptr, bytes)) != hipSuccess) return e;
-    sc->bytes = bytes;
-  } else if (sc->used && (e = hipStreamWaitEvent(stream, sc->done, 0)) != hipSuccess) {
-    return e;
-  }
-  *out = static_cast<char*>(sc->ptr);
+  if ((e = acquire_scratch(sc, bytes, stream)) != hipSuccess) return e;
+  *out = sc->buf.as<char>();
   return hipSuccess;
 }
 
-// After the last kernel of a pass that reads the scratch.
-hipError_t release_scratch(Scratch* sc, hipStream_t stream) {
-  const hipError_t e = hipEventRecord(sc->done, stream);
-  if (e == hipSuccess) sc->used = true;
-  return e;
-}
-
 }  // namespace
-
-hipError_t free_scratch(Scratch* s) {
-  if (!s) return hipSuccess;
-  hipError_t e = s->used ? hipEventSynchronize(s->done) : hipSuccess;  // the last pass may still read it
-  const hipError_t f = s->ptr ? hipFree(s->ptr) : hipSuccess;
-  const hipError_t g = s->done ? hipEventDestroy(s->done) : hipSuccess;
-  if (s->flag) (void)hipFree(s->flag);
-  s->flag = nullptr;
-  s->ptr = nullptr;
-  s->bytes = 0;
-  s->done = nullptr;
-  s->used = false;
-  return e != hipSuccess ? e : f != hipSuccess ? f : g;
-}
 
 // A range whose primes reach above kWheelMaxPrime: bucketed passes.
 hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,

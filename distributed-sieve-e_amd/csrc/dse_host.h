@@ -1,0 +1,109 @@
+// dse_host.h -- shared by the two units of the C-ABI host layer (dse_host.cpp:
+// contexts, tables, collectives, sieve entry points; dse_finish_host.cpp: the
+// primes{k}.txt writers). Not installed; include/dse.h is the ABI.
+#pragma once
+#include <rccl/rccl.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/dse.h"
+#include "dse_internal.h"
+
+#pragma GCC visibility push(hidden)  // private to the host layer: libdse.so's exports stay as they are
+namespace dse {
+
+// Sets the calling thread's dse_last_error / dse_last_status; returns `code`.
+int32_t fail(int32_t code, const std::string& msg);
+
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess)                                                                      \
+      return dse::fail(DSE_EHIP, std::string(#expr " failed: ") + hipGetErrorString(e_));      \
+  } while (0)
+
+#define NCCL_TRY(expr)                                                                         \
+  do {                                                                                         \
+    ncclResult_t r_ = (expr);                                                                  \
+    if (r_ != ncclSuccess)                                                                     \
+      return dse::fail(DSE_ENCCL, std::string(#expr " failed: ") + ncclGetErrorString(r_));    \
+  } while (0)
+
+// Device finish (dse_finish.hip): the tile-sum scratch of the three launches
+// (`done` recorded after the emit launch), and the slab pipeline of the file
+// entry points: two device and two pinned host text buffers of `buf_bytes`
+// each (at most kFinishBufMax), grown on demand.
+struct FinishState {
+  StreamScratch sums;
+  Buf dtext[2];
+  Buf htext[2] = {{nullptr, 0, true}, {nullptr, 0, true}};
+  uint64_t buf_bytes = 0;                 // all four text buffers hold this much
+  unsigned long long* dtotals = nullptr;  // device [2][2]
+  unsigned long long* htotals = nullptr;  // pinned [2][2]
+  hipStream_t copy = nullptr;             // the text's D2H copies
+  hipEvent_t fmt_ev[2] = {nullptr, nullptr};
+  hipEvent_t copy_ev[2] = {nullptr, nullptr};
+};
+
+struct DevState {
+  int device = 0;
+  int num_cus = 0;
+  hipStream_t stream = nullptr;
+  Buf table;
+  Buf counts;                // device scratch (unsigned long long)
+  Buf scratch_mask;          // for dse_sieve_chunk
+  Scratch scratch;           // bucketed-pass scratch (high-offset ranges)
+  FinishState fin;           // device finish: scratch and slab buffers
+  hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
+};
+
+// The chunk masks dse_sieve_all keeps on the devices, with the call they were
+// sieved for: chunk k's mask is masks[k - 1], on device (k - 1) mod #devices.
+// `valid` only after every mask of that call was allocated; a failed
+// allocation frees them all.
+struct ResidentSet {
+  bool valid = false;
+  int64_t n = 0;
+  int32_t P = 0;
+  int64_t cs = 0;                // candidates per chunk
+  uint64_t words = 0;            // uint64 words per mask
+  std::vector<Buf> masks;        // [P], of `words` uint64 each
+};
+
+}  // namespace dse
+
+struct dse_ctx {
+  std::vector<dse::DevState> devs;
+  std::vector<ncclComm_t> comms;
+  dse::ResidentSet resident;
+  dse::SieveOpts opts;  // test-only knobs (dse_debug_set_option)
+  uint64_t finish_slab_words = 0;  // test-only: > 0 caps a finish slab at that many mask words
+  // dse_debug_init_logical: every DevState on device 0, the collectives
+  // replaced by copies (xfer_table / allreduce_counts); on device 0:
+  bool logical = false;
+  // dse_debug_set_option("rccl_single"): a one-device context with a 1-rank
+  // RCCL communicator, so share_table / allreduce_counts issue the real
+  // grouped ncclBroadcast / ncclAllReduce on a one-GPU box.
+  bool rccl_single = false;
+  int64_t rccl_calls = 0;          // collectives RCCL accepted (dse_debug_get_stat)
+  int64_t table_local_builds = 0;  // tables built per device instead of broadcast (share_table)
+  dse::Buf lg_stage;               // gathered counts [devs][n]
+  dse::Buf lg_sum;                 // their sum [n]
+  hipEvent_t lg_done = nullptr;    // the sum on device 0's stream
+};
+
+namespace dse {
+
+// cs = candidates per chunk of (n, P); nums = the odd candidates 3..n
+int32_t chunk_geometry(int64_t n, int32_t P, int64_t* cs, int64_t* nums = nullptr);
+int32_t check_odd_range(uint64_t g_start, uint64_t nbits);
+// keep_dev: sieve into d.scratch_mask even without a host mask (dse_finish_range_file)
+int32_t sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t nbits, uint64_t* mask_or_null,
+                         uint64_t* count, bool keep_dev = false);
+// The device and mask of resident chunk my_num; DSE_EINVAL when it is not resident.
+int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mask);
+void free_finish(FinishState& f);  // dse_finish_host.cpp; the state's device current
+
+}  // namespace dse
+#pragma GCC visibility pop

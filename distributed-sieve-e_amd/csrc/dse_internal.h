@@ -1,6 +1,7 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
-// dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip) and the C-ABI host layer
-// (dse_host.cpp). Not installed; include/dse.h is the ABI.
+// dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip) and the
+// C-ABI host layer (dse_host.cpp, dse_finish_host.cpp). Not installed; include/dse.h
+// is the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,19 +66,52 @@ constexpr uint64_t kBaseLimitMax = 2ull * 150u * 1024u * 8u + 1ull;  // 150 KiB 
 // Big tables: odd primes < 2^31 (so p + SEG fits 32 bits in the kernel).
 constexpr uint64_t kBigBaseLimitMax = (1ull << 31) - 1;
 
-// Device scratch of one context (bucketed pass of high-offset ranges). Grows
-// on demand, freed by free_scratch (dse_destroy). `done` is recorded on the
-// stream of every pass after its last kernel that reads the buffer (any
-// stream, the null stream included): the next pass's stream waits on it
-// (hipStreamWaitEvent, no host block) and a grow or a free synchronises on it.
-struct Scratch {
+// floor(sqrt(x)) for any x < 2^63 (the double root is off by a few at most;
+// (r + 1)^2 stays below 2^64).
+inline uint64_t isqrt64(uint64_t x) {
+  uint64_t r = (uint64_t)__builtin_sqrt((double)x);
+  while (r * r > x) --r;
+  while ((r + 1) * (r + 1) <= x) ++r;
+  return r;
+}
+
+// Grow-only buffer of device memory (pinned: of page-locked host memory).
+// grow_buf is a no-op while the buffer holds `bytes`; otherwise it frees the
+// old allocation (the contents are lost) and allocates exactly `bytes`. The
+// caller guarantees that nothing in flight still uses the old one.
+// (dse_host.cpp)
+struct Buf {
   void* ptr = nullptr;
   uint64_t bytes = 0;
+  bool pinned = false;
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(ptr);
+  }
+};
+hipError_t grow_buf(Buf* b, uint64_t bytes);
+hipError_t free_buf(Buf* b);
+
+// A device scratch buffer shared by calls on any streams (the null stream
+// included), ordered by an event. release_scratch records `done` on the
+// stream of a user after its last kernel that touches the buffer;
+// acquire_scratch makes the next user's stream wait on it (hipStreamWaitEvent,
+// no host block), and a grow or free_scratch synchronises on it on the host
+// before the buffer is freed. Every exit after an acquire must release.
+// (dse_host.cpp)
+struct StreamScratch {
+  Buf buf;
   hipEvent_t done = nullptr;  // created on first use
   bool used = false;          // `done` has been recorded since the last grow
-  uint32_t* flag = nullptr;   // device {sticky overflow, this pass's overflow} (bucket capacity)
 };
-hipError_t free_scratch(Scratch* s);
+hipError_t acquire_scratch(StreamScratch* s, uint64_t bytes, hipStream_t stream);
+hipError_t release_scratch(StreamScratch* s, hipStream_t stream);
+hipError_t free_scratch(StreamScratch* s);
+
+// Device scratch of one context's bucketed passes (high-offset ranges).
+struct Scratch : StreamScratch {
+  uint32_t* flag = nullptr;  // device {sticky overflow, this pass's overflow} (bucket capacity); freed by dse_destroy
+};
 
 // Test-only knobs, set through dse_debug_set_option (include/dse.h); the
 // defaults are the production configuration. No environment variable is read.
@@ -92,7 +126,6 @@ struct SieveOpts {
   uint64_t table_bcast_max = 0;   // > 0: broadcast cap of share_table in bytes (0: DSE_TABLE_BROADCAST_MAX_BYTES)
 };
 
-hipError_t launch_base_primes(uint64_t limit, void* table, uint32_t cap, hipStream_t stream);
 // out[j] = sum_i in[i * n + j], i < nsrc (dse_debug_init_logical's count all-reduce)
 hipError_t launch_sum_rows(const unsigned long long* in, uint32_t nsrc, uint32_t n, unsigned long long* out,
                            hipStream_t stream);

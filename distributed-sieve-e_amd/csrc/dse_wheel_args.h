@@ -46,13 +46,6 @@ WheelRange make_wheel_range(const RangeSpec& rs, uint64_t* plane_lut) {
   return w;
 }
 
-uint64_t isqrt64(uint64_t x) {
-  uint64_t r = (uint64_t)__builtin_sqrt((double)x);
-  while (r * r > x) --r;
-  while ((r + 1) * (r + 1) <= x) ++r;
-  return r;
-}
-
 // A launch over the ranges rs[0..n) (1 <= n <= kMaxRanges, each < 2^31
 // segments in all), their segments in order; thresholds: odd primes up to
 // kQMax, TA, TB1, TB and wheel_max (<= kWheelMaxPrime: the primes above it are

@@ -486,6 +486,65 @@ def test_debug_option_rejects_unknown(ctx):
             ctx.debug_set_option(name, bad)
 
 
+def test_debug_numeric_options_refuse_out_of_range(oracle):
+    """Every numeric debug option refuses a value below and above its range
+    with DSE_EINVAL and does not store it: a sieve of N = 1e6 afterwards
+    matches the oracle."""
+    import re
+    from mail_sieve_e import _dse
+    from mail_sieve_e import sieve as S
+    src = open(os.path.join(_dse.CSRC, "dse_internal.h")).read()
+    wheel_max_log = int(re.search(r"#define DSE_WHEEL_MAX_LOG (\d+)", src).group(1))
+    u32 = 2**32
+    bad = [("bucket_pass_segments", -1), ("bucket_pass_segments", u32), ("bucket_split_log2", -1),
+           ("bucket_split_log2", 64), ("wheel_geometry", -1), ("wheel_geometry", 3), ("bucket_k0_divisor", -1),
+           ("bucket_k0_divisor", u32), ("scratch_poison", -1), ("scratch_poison", 2),
+           ("table_broadcast_max_bytes", -1), ("finish_slab_words", -1), ("bucket_cap_divisor", -1),
+           ("bucket_cap_divisor", u32), ("bucket_lo_log2", 16), ("bucket_lo_log2", wheel_max_log + 1)]
+    N, P = 10**6, 3
+    _, m_ref, c_ref, _ = oracle.sieve(N, P)
+    for logical in (None, 2):
+        with S.Context(num_gpus=1, logical=logical) as c:
+            for name, value in bad:
+                with pytest.raises(_dse.DseError) as e:
+                    c.debug_set_option(name, value)
+                assert e.value.code == -1, (name, value)
+                assert name in str(e.value), (name, value)
+            counts, _, _ = c.sieve_all(N, P)
+            assert [int(x) for x in counts] == [int(x) for x in c_ref]
+            for k in range(1, P + 1):
+                assert np.array_equal(c.copy_chunk_mask(N, P, k), m_ref[k - 1]), k
+
+
+@pytest.mark.parametrize("logical", [None, 2])
+def test_resident_set_follows_the_last_call(oracle, tmp_path, logical):
+    """The resident masks are those of the last dse_sieve_all: after (N, 3) then
+    (N, 2) chunk 3 is not resident (copy and device finish refuse it with
+    DSE_EINVAL) and chunks 1, 2 are P = 2's; (N, 3) again replaces them, and an
+    identical call (the masks reused) gives the same."""
+    from mail_sieve_e import _dse
+    from mail_sieve_e import sieve as S
+    N = 10**6
+    ref = {P: oracle.sieve(N, P) for P in (2, 3)}
+
+    def check_all(c, P):
+        _, m_ref, c_ref, _ = ref[P]
+        counts, _, _ = c.sieve_all(N, P)
+        assert [int(x) for x in counts] == [int(x) for x in c_ref], P
+        for k in range(1, P + 1):
+            assert np.array_equal(c.copy_chunk_mask(N, P, k), m_ref[k - 1]), (P, k)
+
+    with S.Context(num_gpus=1, logical=logical) as c:
+        c.sieve_all(N, 3)
+        check_all(c, 2)
+        for refused in (lambda: c.copy_chunk_mask(N, 3, 3), lambda: c.finish_resident(str(tmp_path / "p3.txt"), 3)):
+            with pytest.raises(_dse.DseError) as e:
+                refused()
+            assert e.value.code == -1 and "not resident" in str(e.value)
+        check_all(c, 3)
+        check_all(c, 3)  # the same (N, P): the reuse path
+
+
 def test_bucket_overflow_flag(oracle):
     """A bucketed pass over its entry capacity (forced with the test-only
     option bucket_cap_divisor; the production bound is rigorous) must fail

@@ -26,7 +26,7 @@ def sub(s, old, new, count=1):
 
 
 def main(root):
-    out = os.path.join(root, "distributed-sieve-e_amd", "csrc")  # the tree layout dse_host.cpp includes from
+    out = os.path.join(root, "distributed-sieve-e_amd", "csrc")  # the tree layout the host units (dse_host.cpp, dse_finish_host.cpp) include from
     os.makedirs(out, exist_ok=True)
     os.makedirs(os.path.join(root, "include"), exist_ok=True)
     shutil.copy(os.path.join(SRC, "..", "..", "include", "dse.h"), os.path.join(root, "include", "dse.h"))
