@@ -149,7 +149,9 @@ int32_t finish_launch(DevState& d, uint32_t flags, uint64_t g_start, uint64_t nb
   return DSE_OK;
 }
 
-int32_t ensure_finish_bufs(DevState& d, uint64_t want) {
+}  // namespace
+
+int32_t dse::ensure_finish_bufs(DevState& d, uint64_t want) {
   FinishState& f = d.fin;
   if (!f.copy) HIP_TRY(hipStreamCreateWithFlags(&f.copy, hipStreamNonBlocking));
   for (int i = 0; i < 2; ++i) {
@@ -169,6 +171,8 @@ int32_t ensure_finish_bufs(DevState& d, uint64_t want) {
   f.buf_bytes = want;
   return DSE_OK;
 }
+
+namespace {
 
 // The slab pipeline: mask_dev (ready in d.stream's order) -> file. Slab i+1 is
 // formatted on d.stream while slab i's text is copied on the copy stream and

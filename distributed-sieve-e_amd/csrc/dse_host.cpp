@@ -1,6 +1,7 @@
 // dse_host.cpp -- C-ABI host layer of libdse.so (include/dse.h): contexts,
 // chunk geometry, the base table and its sharing, collectives, the sieve entry
-// points, debug options and stats. The finish side is dse_finish_host.cpp.
+// points, debug options and stats. The finish side is dse_finish_host.cpp,
+// primes as numbers dse_primes_host.cpp.
 //
 // Replaces the reference's orchestration of the hot path:
 //   spread-work (sieve.clj:15-34)            -> dse_spread_work (exact int64)
@@ -384,6 +385,8 @@ const struct {
      [](dse_ctx* c, int64_t v) { c->opts.table_bcast_max = (uint64_t)v; }},
     {"finish_slab_words", 0, kI64Max, "must be >= 0",
      [](dse_ctx* c, int64_t v) { c->finish_slab_words = (uint64_t)v; }},
+    {"primes_slab_entries", 0, kI64Max, "must be >= 0",
+     [](dse_ctx* c, int64_t v) { c->primes_slab_entries = (uint64_t)v; }},
 };
 
 }  // namespace
@@ -490,6 +493,7 @@ void dse_destroy(dse_ctx* ctx) {
     (void)free_scratch(&d.scratch);
     if (d.scratch.flag) (void)hipFree(d.scratch.flag);
     free_finish(d.fin);
+    (void)free_scratch(&d.primes_sums);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }
@@ -746,6 +750,8 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     int c = 0;
     if (!ctx->comms.empty()) NCCL_TRY(ncclCommCount(ctx->comms[0], &c));
     *value = c;
+  } else if (n == "primes_tile_bits") {
+    *value = (int64_t)kPrimesTileBits;
   } else {
     return fail(DSE_EINVAL, "unknown stat " + n);
   }

@@ -1,6 +1,7 @@
-// dse_host.h -- shared by the two units of the C-ABI host layer (dse_host.cpp:
+// dse_host.h -- shared by the units of the C-ABI host layer (dse_host.cpp:
 // contexts, tables, collectives, sieve entry points; dse_finish_host.cpp: the
-// primes{k}.txt writers). Not installed; include/dse.h is the ABI.
+// primes{k}.txt writers; dse_primes_host.cpp: primes as numbers). Not
+// installed; include/dse.h is the ABI.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -55,6 +56,7 @@ struct DevState {
   Buf scratch_mask;          // for dse_sieve_chunk
   Scratch scratch;           // bucketed-pass scratch (high-offset ranges)
   FinishState fin;           // device finish: scratch and slab buffers
+  StreamScratch primes_sums; // primes as numbers (dse_primes.hip): tile-sum scratch of the three launches
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
 };
 
@@ -79,6 +81,7 @@ struct dse_ctx {
   dse::ResidentSet resident;
   dse::SieveOpts opts;  // test-only knobs (dse_debug_set_option)
   uint64_t finish_slab_words = 0;  // test-only: > 0 caps a finish slab at that many mask words
+  uint64_t primes_slab_entries = 0;  // test-only: > 0 caps a slab of dse_primes_range / _resident at that many values
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:
   bool logical = false;
@@ -104,6 +107,10 @@ int32_t sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t nbits,
 // The device and mask of resident chunk my_num; DSE_EINVAL when it is not resident.
 int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mask);
 void free_finish(FinishState& f);  // dse_finish_host.cpp; the state's device current
+// The slab pipeline's streams, events, totals and its four buffers of min(max(want, 1 MiB), 64 MiB)
+// bytes each (d.fin, grown on demand; dse_finish_host.cpp). dse_primes_host.cpp moves its values
+// through the same buffers: a blocking entry point drains both streams before it returns.
+int32_t ensure_finish_bufs(DevState& d, uint64_t want);
 
 }  // namespace dse
 #pragma GCC visibility pop

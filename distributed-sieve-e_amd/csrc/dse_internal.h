@@ -1,7 +1,7 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
-// dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip) and the
-// C-ABI host layer (dse_host.cpp, dse_finish_host.cpp). Not installed; include/dse.h
-// is the ABI.
+// dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
+// dse_primes.hip) and the C-ABI host layer (dse_host.cpp, dse_finish_host.cpp,
+// dse_primes_host.cpp). Not installed; include/dse.h is the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -189,5 +189,23 @@ uint64_t finish_scratch_bytes(uint64_t nbits);
 hipError_t launch_finish_text(uint32_t flags, uint64_t g_start, uint64_t nbits, const uint64_t* mask,
                               uint64_t first_rank, void* text, uint64_t text_cap, unsigned long long* totals,
                               void* tile_sums, hipStream_t stream);
+
+// Primes as numbers (dse_primes.hip): the set bits of mask (odd indices
+// [g_start, g_start + nbits), 64-bit words) as uint64 values 3 + 2 (g_start +
+// bit), ranked in increasing order. A tile is kPrimesTileBits candidates.
+// launch_primes_scan: the size and scan launches. tile_sums
+// (primes_scratch_bytes(nbits) bytes of device scratch) gets the tiles' first
+// ranks, one uint64 per tile and the total behind them; totals[0] = entries,
+// totals[1] = min(out_cap, max(0, entries - first)).
+// launch_primes_emit: the emit launch over tiles [tile0, tile0 + tiles) of a
+// scanned tile_sums: the entry of rank r is stored to out[r - first] exactly
+// when first <= r < first + out_cap and one of those tiles holds it.
+constexpr uint32_t kPrimesTileBits = 256 * 64;
+uint64_t primes_scratch_bytes(uint64_t nbits);
+hipError_t launch_primes_scan(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first,
+                              uint64_t out_cap, unsigned long long* totals, void* tile_sums, hipStream_t stream);
+hipError_t launch_primes_emit(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first, uint64_t* out,
+                              uint64_t out_cap, const void* tile_sums, uint64_t tile0, uint64_t tiles,
+                              hipStream_t stream);
 
 }  // namespace dse

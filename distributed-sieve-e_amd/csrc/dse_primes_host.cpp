@@ -1,0 +1,180 @@
+// dse_primes_host.cpp -- primes as numbers, the host side (include/dse.h): a
+// device-resident mask becomes uint64 prime values on the device
+// (dse_primes.hip), in the caller's device buffer (dse_primes_dev_async) or, in
+// slabs through pinned memory, in a host buffer (dse_primes_range,
+// dse_primes_resident).
+#include <algorithm>
+#include <cstring>
+
+#include "dse_host.h"
+#include "dse_primes_word.h"
+
+using namespace dse;
+
+namespace {
+
+// what every entry point refuses of a range
+int32_t primes_check_range(uint64_t g_start, uint64_t nbits) {
+  if (int32_t rc = check_odd_range(g_start, nbits)) return rc;
+  if (nbits > (1ull << 44)) return fail(DSE_ERANGE, "primes range above 2^44 candidates in one call");
+  return DSE_OK;
+}
+
+// The tile-sum scratch of the device, ordered against whatever stream used it last.
+int32_t primes_acquire(DevState& d, uint64_t nbits, hipStream_t stream) {
+  StreamScratch& sums = d.primes_sums;
+  // a grow takes half as much again, 64 KiB at least
+  const uint64_t need = primes_scratch_bytes(nbits);
+  HIP_TRY(acquire_scratch(&sums, sums.buf.bytes >= need ? need : std::max<uint64_t>(need + need / 2, 1ull << 16),
+                          stream));
+  return DSE_OK;
+}
+
+// The slab pipeline: mask_dev (ready in d.stream's order) -> out. The size and
+// scan launches run once; the scanned tile sums are copied to the host, and
+// every slab of at most `slab` ranks is emitted over the tiles that hold its
+// ranks (the sums are monotone: two binary searches). Slab i + 1 is emitted on
+// d.stream while slab i's values are copied on the copy stream and slab i - 1
+// is copied into the caller's memory by this thread.
+int32_t primes_pipeline(dse_ctx* ctx, DevState& d, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
+                        uint64_t first, uint64_t* out, uint64_t out_cap, uint64_t* total, uint64_t* written) {
+  if (total) *total = 0;
+  if (written) *written = 0;
+  if (!nbits) return DSE_OK;
+  int32_t rc;
+  const uint64_t want = out_cap > (1ull << 40) ? ~0ull : out_cap * 8;
+  if ((rc = ensure_finish_bufs(d, want))) return rc;
+  FinishState& f = d.fin;
+  const uint64_t ntiles = (nbits + kPrimesTileBits - 1) / kPrimesTileBits;
+  std::vector<unsigned long long> hsums;
+  bool acquired = false;
+
+  auto run = [&]() -> int32_t {
+    int32_t r;
+    if ((r = primes_acquire(d, nbits, d.stream))) return r;
+    acquired = true;
+    void* const sums = d.primes_sums.buf.ptr;
+    HIP_TRY(launch_primes_scan(g_start, nbits, mask_dev, first, out_cap, f.dtotals, sums, d.stream));
+    HIP_TRY(hipMemcpyAsync(f.htotals, f.dtotals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    const uint64_t cnt = f.htotals[0], n_out = f.htotals[1];
+    if (total) *total = cnt;
+    if (!n_out) return DSE_OK;
+    hsums.resize(ntiles + 1);
+    HIP_TRY(hipMemcpyAsync(hsums.data(), sums, (ntiles + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+
+    uint64_t slab = f.buf_bytes / 8;
+    if (ctx->primes_slab_entries) slab = std::min(slab, ctx->primes_slab_entries);
+    bool copy_pending[2] = {false, false};
+    int prev_slot = -1;
+    uint64_t prev_off = 0, prev_n = 0;
+    auto take = [&](int slot, uint64_t off, uint64_t n) -> int32_t {  // once the slab's copy has run
+      HIP_TRY(hipEventSynchronize(f.copy_ev[slot]));
+      std::memcpy(out + off, f.htext[slot].ptr, n * 8);
+      return DSE_OK;
+    };
+    int slot = 0;
+    for (uint64_t off = 0; off < n_out; off += slab, slot ^= 1) {
+      const uint64_t n = std::min(slab, n_out - off), ra = first + off, rb = ra + n;
+      // tiles [t0, t1): the last tile that starts at or below rank ra, up to the first that starts at or above rb
+      const uint64_t t0 = (uint64_t)(std::upper_bound(hsums.begin(), hsums.begin() + ntiles, ra) - hsums.begin()) - 1;
+      const uint64_t t1 = (uint64_t)(std::lower_bound(hsums.begin(), hsums.begin() + ntiles, rb) - hsums.begin());
+      uint64_t* const dv = f.dtext[slot].as<uint64_t>();
+      // the slot's device buffer is free once the copy of the slab that used it has run
+      if (copy_pending[slot]) HIP_TRY(hipStreamWaitEvent(d.stream, f.copy_ev[slot], 0));
+      HIP_TRY(launch_primes_emit(g_start, nbits, mask_dev, ra, dv, n, sums, t0, t1 - t0, d.stream));
+      HIP_TRY(hipEventRecord(f.fmt_ev[slot], d.stream));
+      HIP_TRY(hipStreamWaitEvent(f.copy, f.fmt_ev[slot], 0));
+      HIP_TRY(hipMemcpyAsync(f.htext[slot].ptr, dv, n * 8, hipMemcpyDeviceToHost, f.copy));
+      HIP_TRY(hipEventRecord(f.copy_ev[slot], f.copy));
+      copy_pending[slot] = true;
+      if (prev_slot >= 0 && (r = take(prev_slot, prev_off, prev_n))) return r;
+      prev_slot = slot;
+      prev_off = off;
+      prev_n = n;
+    }
+    if ((r = take(prev_slot, prev_off, prev_n))) return r;
+    if (written) *written = n_out;
+    return DSE_OK;
+  };
+  rc = run();
+  if (acquired) {
+    const hipError_t e = release_scratch(&d.primes_sums, d.stream);
+    if (e != hipSuccess && !rc) rc = fail(DSE_EHIP, std::string("release_scratch failed: ") + hipGetErrorString(e));
+  }
+  if (rc) {  // leave nothing in flight on the buffers
+    (void)hipStreamSynchronize(d.stream);
+    if (f.copy) (void)hipStreamSynchronize(f.copy);
+  }
+  return rc;
+}
+
+int32_t primes_check_out(const uint64_t* out, uint64_t out_cap) {
+  if (out_cap && !out) return fail(DSE_EINVAL, "null out with a non-zero capacity");
+  return DSE_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t dse_primes_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
+                                        uint64_t first, uint64_t* out_dev, uint64_t out_cap, uint64_t* totals_dev,
+                                        void* stream) {
+  if (!ctx || !totals_dev) return fail(DSE_EINVAL, "null ctx or totals");
+  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
+  int32_t rc = primes_check_out(out_dev, out_cap);
+  if (rc) return rc;
+  if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
+  if ((rc = primes_check_range(g_start, nbits))) return rc;
+  DevState& d = ctx->devs[0];
+  HIP_TRY(hipSetDevice(d.device));
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = primes_acquire(d, nbits, s))) return rc;
+  void* const sums = d.primes_sums.buf.ptr;
+  hipError_t e = launch_primes_scan(g_start, nbits, mask_dev, first, out_cap,
+                                    reinterpret_cast<unsigned long long*>(totals_dev), sums, s);
+  if (e == hipSuccess)
+    e = launch_primes_emit(g_start, nbits, mask_dev, first, out_dev, out_cap, sums, 0,
+                           (nbits + kPrimesTileBits - 1) / kPrimesTileBits, s);
+  HIP_TRY(release_scratch(&d.primes_sums, s));  // also after a failure: what was launched may read the scratch
+  if (e != hipSuccess) return fail(DSE_EHIP, std::string("primes launch failed: ") + hipGetErrorString(e));
+  return DSE_OK;
+}
+
+extern "C" int32_t dse_primes_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, uint64_t first, uint64_t* out,
+                                    uint64_t out_cap, uint64_t* total, uint64_t* written) {
+  if (!ctx) return fail(DSE_EINVAL, "null ctx");
+  int32_t rc = primes_check_out(out, out_cap);
+  if (rc) return rc;
+  if ((rc = primes_check_range(g_start, nbits))) return rc;
+  DevState& d = ctx->devs[0];
+  if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
+  return primes_pipeline(ctx, d, g_start, nbits, d.scratch_mask.as<uint64_t>(), first, out, out_cap, total, written);
+}
+
+extern "C" int32_t dse_primes_resident(dse_ctx* ctx, int32_t my_num, uint64_t first, uint64_t* out,
+                                       uint64_t out_cap, uint64_t* total, uint64_t* written) {
+  if (!ctx) return fail(DSE_EINVAL, "null ctx");
+  int32_t rc = primes_check_out(out, out_cap);
+  if (rc) return rc;
+  DevState* d;
+  uint64_t* mask;
+  if ((rc = find_resident(ctx, my_num, &d, &mask))) return rc;
+  const uint64_t cs = (uint64_t)ctx->resident.cs;
+  const uint64_t g_start = (uint64_t)(my_num - 1) * cs;
+  if ((rc = primes_check_range(g_start, cs))) return rc;
+  HIP_TRY(hipSetDevice(d->device));
+  return primes_pipeline(ctx, *d, g_start, cs, mask, first, out, out_cap, total, written);
+}
+
+extern "C" int32_t dse_debug_primes_word(uint64_t word, uint64_t g_word_start, uint64_t rank0, uint64_t first,
+                                         uint64_t cap, uint64_t out[64]) {
+  if (!out) return fail(DSE_EINVAL, "null out");
+  if (g_word_start > (1ull << 62) - 64 || rank0 > (1ull << 62))
+    return fail(DSE_ERANGE, "word or rank beyond 2^62");
+  uint32_t n = 0;
+  uint64_t bits = word, rank = rank0;
+  primes_word(bits, rank, g_word_start, first, primes_window_end(first, cap), [&](uint64_t, uint64_t v) { out[n++] = v; });
+  return (int32_t)n;
+}

@@ -24,6 +24,10 @@ ERRORS = {
     -7: "DSE_EINTERNAL",
 }
 
+# Candidates per tile of the dse_primes_* kernels (csrc/dse_internal.h
+# kPrimesTileBits; dse_debug_get_stat "primes_tile_bits" reports the library's).
+PRIMES_TILE_BITS = 256 * 64
+
 # name -> (restype, argtypes); every symbol include/dse.h declares.
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _vp, _cp = ctypes.c_void_p, ctypes.c_char_p
@@ -59,7 +63,11 @@ SIGNATURES = {
     "dse_finish_text_dev_async": (_i32, [_vp, ctypes.c_uint32, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
     "dse_finish_resident_file": (_i32, [_vp, _cp, _i32]),
     "dse_finish_range_file": (_i32, [_vp, _cp, _i32, _u64, _u64, _pu64]),
+    "dse_primes_dev_async": (_i32, [_vp, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "dse_primes_range": (_i32, [_vp, _u64, _u64, _u64, _pu64, _u64, _pu64, _pu64]),
+    "dse_primes_resident": (_i32, [_vp, _i32, _u64, _pu64, _u64, _pu64, _pu64]),
     "dse_debug_finish_format": (_i32, [_u64, ctypes.c_uint32, ctypes.c_char_p]),
+    "dse_debug_primes_word": (_i32, [_u64, _u64, _u64, _u64, _u64, _pu64]),
     "dse_debug_set_option": (_i32, [_vp, _cp, _i64]),
     "dse_debug_init_logical": (_vp, [_i32]),
     "dse_debug_get_stat": (_i32, [_vp, _cp, _pi64]),

@@ -156,6 +156,53 @@ class Context:
               "dse_finish_range_file")
         return cnt.value
 
+    # -- primes as numbers ------------------------------------------------------
+    def primes_dev_async(self, g_start: int, nbits: int, mask_ptr: int, first: int, out_ptr: int, out_cap: int,
+                         totals_ptr: int, stream_ptr: int = 0):
+        """The device mask's set bits as uint64 values 3 + 2 (g_start + bit) in
+        device memory (include/dse.h dse_primes_dev_async): out[i] = the entry of
+        rank first + i; totals[0] = entries of the range, totals[1] = written."""
+        check(lib().dse_primes_dev_async(self.ptr, g_start, nbits, mask_ptr or None, first, out_ptr or None,
+                                         out_cap, totals_ptr, stream_ptr or None),
+              "dse_primes_dev_async")
+
+    def _primes(self, where: str, call, first: int, count: Optional[int]) -> np.ndarray:
+        """call(first, out, cap, total, written) with an exactly sized buffer:
+        count=None asks for the total first (a call with no output)."""
+        tot, wr = ctypes.c_uint64(), ctypes.c_uint64()
+        if count is None:
+            check(call(first, None, 0, ctypes.byref(tot), ctypes.byref(wr)), where)
+            count = max(0, tot.value - first)
+        out = np.empty(count, dtype=np.uint64)
+        check(call(first, u64p(out) if count else None, count, ctypes.byref(tot), ctypes.byref(wr)), where)
+        return out[:wr.value]
+
+    def primes_range(self, g_start: int, nbits: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """gen-table + sieve-e of an odd-index range, and its primes as uint64
+        values extracted on the device: the entries of ranks [first, first +
+        count) in increasing order (count=None: every one from `first` on)."""
+        L = lib()
+        return self._primes("dse_primes_range",
+                            lambda f, o, c, t, w: L.dse_primes_range(self.ptr, g_start, nbits, f, o, c, t, w),
+                            first, count)
+
+    def resident_primes(self, my_num: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The same for a chunk the last sieve_all left on its device: the mask
+        never reaches the host, only the values asked for do."""
+        L = lib()
+        return self._primes("dse_primes_resident",
+                            lambda f, o, c, t, w: L.dse_primes_resident(self.ptr, my_num, f, o, c, t, w),
+                            first, count)
+
+    def primes_window(self, lo: int, hi: int) -> np.ndarray:
+        """The odd primes in [max(lo, 3), hi] (sieve_window's convention: its
+        count is this array's length)."""
+        a = max(lo, 3) | 1
+        if hi < a:
+            return np.empty(0, dtype=np.uint64)
+        b = hi if hi & 1 else hi - 1
+        return self.primes_range((a - 3) // 2, (b - a) // 2 + 1)
+
 
 def base_table_bytes(limit: int) -> int:
     return int(lib().dse_base_table_bytes(limit))

@@ -232,6 +232,40 @@ int32_t dse_finish_resident_file(dse_ctx *ctx, const char *path, int32_t my_num)
 int32_t dse_finish_range_file(dse_ctx *ctx, const char *path, int32_t my_num,
                               uint64_t g_start, uint64_t nbits, uint64_t *count);
 
+/* ---- primes as numbers --------------------------------------------------- */
+
+/* The set bits of a device-resident mask as little-endian uint64 prime values
+ * 3 + 2(g_start + bit index), in increasing order, extracted on the GPU. The
+ * entries of a range are ranked 0, 1, 2, ... in that order; a call returns the
+ * rank window [first, first + out_cap), so a large range can be paged through
+ * a small buffer and a count costs no output at all. Bits past nbits in the
+ * last word are ignored. DSE_ERANGE for a range beyond 2^62 or more than 2^44
+ * candidates in one call. */
+
+/* Async on stream. totals_dev[0] = set bits of the range (always written);
+ * totals_dev[1] = elements written = min(out_cap, max(0, total - first)).
+ * out_dev[i] = value of the entry of rank first + i. Nothing outside
+ * [out_dev, out_dev + totals_dev[1]) is touched; out_dev may be NULL when
+ * out_cap == 0 (count only). out_dev must be 8-byte aligned. DSE_EINVAL for a
+ * null ctx or totals, a null mask with nbits > 0, a null out_dev with
+ * out_cap > 0, or a misaligned out_dev. */
+int32_t dse_primes_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                             const uint64_t *mask_dev, uint64_t first,
+                             uint64_t *out_dev, uint64_t out_cap,
+                             uint64_t *totals_dev, void *stream);
+
+/* gen-table + sieve-e + extraction of an odd-index range, on the first device; host buffer.
+ * *total = primes of the range, *written = values stored to out (either may be NULL); the range
+ * rules of dse_sieve_odd_range apply. The values cross to the host in slabs through the two device
+ * and two pinned host buffers of the device finish (dse_finish_resident_file): a slab is extracted
+ * while the one before it is copied to the host and the one before that is copied into out. */
+int32_t dse_primes_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, uint64_t first,
+                         uint64_t *out, uint64_t out_cap, uint64_t *total, uint64_t *written);
+
+/* The same for chunk my_num left resident by the last dse_sieve_all; DSE_EINVAL if not resident. */
+int32_t dse_primes_resident(dse_ctx *ctx, int32_t my_num, uint64_t first,
+                            uint64_t *out, uint64_t out_cap, uint64_t *total, uint64_t *written);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -268,6 +302,8 @@ int32_t dse_finish_range_file(dse_ctx *ctx, const char *path, int32_t my_num,
  *   communicator, no collective for one device).
  *   "finish_slab_words" = k > 0: dse_finish_resident_file / dse_finish_range_file
  *   format slabs of at most k mask words (slab seams on tiny inputs); 0 = default.
+ *   "primes_slab_entries" = k > 0: dse_primes_range / dse_primes_resident move
+ *   slabs of at most k values (slab seams on tiny inputs); 0 = default.
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -276,7 +312,8 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   "rccl_comms": communicators the context holds;
  *   "rccl_ranks": ranks of its communicator as ncclCommCount reports (0: none);
  *   "table_local_builds": base tables built on a device of their own instead
- *   of broadcast (one per device and call).
+ *   of broadcast (one per device and call);
+ *   "primes_tile_bits": candidates per tile of the dse_primes_* kernels.
  * DSE_EINVAL for an unknown name. */
 int32_t dse_debug_get_stat(dse_ctx *ctx, const char *name, int64_t *value);
 
@@ -307,6 +344,16 @@ int32_t dse_debug_expand_block(int32_t variant, const uint32_t planes[8], uint32
  * terminator; at most 24 bytes). Test-only; DSE_EINVAL (negative) for a null
  * pointer or a flag other than DSE_FINISH_DOUBLES. */
 int32_t dse_debug_finish_format(uint64_t v, uint32_t flags, char out[32]);
+
+/* The dse_primes_* emit kernel's own per-word body, run on the host (no device
+ * call): word's set bits are entries of ranks rank0, rank0 + 1, ... in
+ * increasing bit order, bit b having the value 3 + 2(g_word_start + b). The
+ * values of the entries whose rank lies in [first, first + cap) are written to
+ * out[0], out[1], ... in that order; returns how many (0..64). Test-only;
+ * negative: DSE_EINVAL for a null pointer, DSE_ERANGE for g_word_start + 64 or
+ * rank0 above 2^62. */
+int32_t dse_debug_primes_word(uint64_t word, uint64_t g_word_start, uint64_t rank0, uint64_t first,
+                              uint64_t cap, uint64_t out[64]);
 
 #ifdef __cplusplus
 }
