@@ -188,7 +188,12 @@ int32_t dse_base_table_finish_dev_async(dse_ctx *ctx, uint64_t limit, void *tabl
  * *count_dev (device uint64) is INCREMENTED by the prime count (zero it
  * first). Asynchronous on stream. A device-side failure (DSE_EINTERNAL: a
  * bucket pass over its entry capacity, a rigorous bound, so never expected)
- * sets bit 63 of *count_dev and is reported by dse_device_status. */
+ * sets bit 63 of *count_dev and is reported by dse_device_status.
+ * Nothing outside [mask_dev, mask_dev + ceil(nbits/64)) is written, and the
+ * last word's bits past nbits are stored as 0. nbits = 0 returns DSE_OK and
+ * launches nothing: neither the mask nor *count_dev is touched. The table
+ * must hold every odd prime <= dse_base_limit_for_range(g_start, nbits); a
+ * larger table serves as well. */
 int32_t dse_sieve_range_dev_async(dse_ctx *ctx, const void *table_dev, uint64_t g_start,
                                   uint64_t nbits, uint64_t *mask_dev, uint64_t *count_dev,
                                   void *stream);
