@@ -387,6 +387,7 @@ const struct {
      [](dse_ctx* c, int64_t v) { c->finish_slab_words = (uint64_t)v; }},
     {"primes_slab_entries", 0, kI64Max, "must be >= 0",
      [](dse_ctx* c, int64_t v) { c->primes_slab_entries = (uint64_t)v; }},
+    {"stats_grid", 0, (int64_t)kStatsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->stats_grid = (uint32_t)v; }},
 };
 
 }  // namespace
@@ -494,6 +495,7 @@ void dse_destroy(dse_ctx* ctx) {
     if (d.scratch.flag) (void)hipFree(d.scratch.flag);
     free_finish(d.fin);
     (void)free_scratch(&d.primes_sums);
+    (void)free_scratch(&d.stats_scratch);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }
@@ -752,6 +754,8 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     *value = c;
   } else if (n == "primes_tile_bits") {
     *value = (int64_t)kPrimesTileBits;
+  } else if (n == "stats_tile_bits") {
+    *value = (int64_t)kStatsTileBits;
   } else {
     return fail(DSE_EINVAL, "unknown stat " + n);
   }

@@ -1,7 +1,8 @@
 // dse_host.h -- shared by the units of the C-ABI host layer (dse_host.cpp:
 // contexts, tables, collectives, sieve entry points; dse_finish_host.cpp: the
-// primes{k}.txt writers; dse_primes_host.cpp: primes as numbers). Not
-// installed; include/dse.h is the ABI.
+// primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
+// dse_stats_host.cpp: statistics of a mask). Not installed; include/dse.h is
+// the ABI.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -57,6 +58,7 @@ struct DevState {
   Scratch scratch;           // bucketed-pass scratch (high-offset ranges)
   FinishState fin;           // device finish: scratch and slab buffers
   StreamScratch primes_sums; // primes as numbers (dse_primes.hip): tile-sum scratch of the three launches
+  StreamScratch stats_scratch; // statistics (dse_stats.hip): the workgroups' slabs, and results on their way to the host
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
 };
 
@@ -82,6 +84,7 @@ struct dse_ctx {
   dse::SieveOpts opts;  // test-only knobs (dse_debug_set_option)
   uint64_t finish_slab_words = 0;  // test-only: > 0 caps a finish slab at that many mask words
   uint64_t primes_slab_entries = 0;  // test-only: > 0 caps a slab of dse_primes_range / _resident at that many values
+  uint32_t stats_grid = 0;  // test-only: > 0 caps the workgroups of a statistics launch
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:
   bool logical = false;

@@ -1,7 +1,8 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
-// dse_primes.hip) and the C-ABI host layer (dse_host.cpp, dse_finish_host.cpp,
-// dse_primes_host.cpp). Not installed; include/dse.h is the ABI.
+// dse_primes.hip, dse_stats.hip) and the C-ABI host layer (dse_host.cpp,
+// dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp). Not installed;
+// include/dse.h is the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -207,5 +208,19 @@ hipError_t launch_primes_scan(uint64_t g_start, uint64_t nbits, const uint64_t* 
 hipError_t launch_primes_emit(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first, uint64_t* out,
                               uint64_t out_cap, const void* tile_sums, uint64_t tile0, uint64_t tiles,
                               hipStream_t stream);
+
+// Statistics of a mask (dse_stats.hip): the main launch over `grid` workgroups,
+// each walking its own run of tiles of kStatsTileBits candidates, and the
+// closing launch, which writes the dse_stats (kStatsWords uint64 words) at
+// `stats`. grid = stats_grid(nbits, CUs of the device, cap or 0): 0 exactly for
+// an empty range, at most kStatsMaxGrid. slabs: stats_scratch_bytes(grid) bytes
+// of device scratch. patterns: npatterns <= 8 host values, passed by value.
+constexpr uint32_t kStatsTileBits = 256 * 64;
+constexpr uint32_t kStatsMaxGrid = 1024;
+constexpr uint32_t kStatsWords = 27 + 1024;
+uint32_t stats_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
+uint64_t stats_scratch_bytes(uint32_t grid);
+hipError_t launch_stats(uint64_t g_start, uint64_t nbits, const uint64_t* mask, const uint32_t* patterns,
+                        uint32_t npatterns, uint64_t* stats, void* slabs, uint32_t grid, hipStream_t stream);
 
 }  // namespace dse

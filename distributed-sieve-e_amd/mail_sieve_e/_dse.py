@@ -28,10 +28,14 @@ ERRORS = {
 # kPrimesTileBits; dse_debug_get_stat "primes_tile_bits" reports the library's).
 PRIMES_TILE_BITS = 256 * 64
 
+# include/dse.h dse_stats as uint64 words, and where its members start
+STATS_WORDS, STATS_GAP_BINS, STATS_MAX_PATTERNS, STATS_NONE = 27 + 1024, 1024, 8, (1 << 64) - 1
+
 # name -> (restype, argtypes); every symbol include/dse.h declares.
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _vp, _cp = ctypes.c_void_p, ctypes.c_char_p
 _pi64, _pu64 = ctypes.POINTER(_i64), ctypes.POINTER(_u64)
+_u32, _pu32 = ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)
 SIGNATURES = {
     "dse_version": (_cp, []),
     "dse_last_error": (_cp, []),
@@ -66,6 +70,11 @@ SIGNATURES = {
     "dse_primes_dev_async": (_i32, [_vp, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
     "dse_primes_range": (_i32, [_vp, _u64, _u64, _u64, _pu64, _u64, _pu64, _pu64]),
     "dse_primes_resident": (_i32, [_vp, _i32, _u64, _pu64, _u64, _pu64, _pu64]),
+    "dse_stats_dev_async": (_i32, [_vp, _u64, _u64, _vp, _pu32, _u32, _vp, _vp]),
+    "dse_stats_range": (_i32, [_vp, _u64, _u64, _pu32, _u32, _pu64]),
+    "dse_stats_resident": (_i32, [_vp, _i32, _pu32, _u32, _pu64]),
+    "dse_stats_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_debug_stats_host": (_i32, [_pu64, _u64, _u64, _pu32, _u32, _pu64]),
     "dse_debug_finish_format": (_i32, [_u64, ctypes.c_uint32, ctypes.c_char_p]),
     "dse_debug_primes_word": (_i32, [_u64, _u64, _u64, _u64, _u64, _pu64]),
     "dse_debug_set_option": (_i32, [_vp, _cp, _i64]),

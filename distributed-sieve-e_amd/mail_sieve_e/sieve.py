@@ -26,6 +26,113 @@ from . import _dse
 from ._dse import check, lib, u64p
 
 
+# Constellation patterns (include/dse.h "statistics of a mask"): bit j set means
+# the candidate j places above, the value p + 2j, must be prime too.
+def pattern(*diffs: int) -> int:
+    """The pattern of the primes p + d for the even differences d: pattern(0, 2, 6) == 0b1011."""
+    m = 0
+    for d in diffs:
+        if d < 0 or d > 62 or d % 2:
+            raise ValueError("differences are even and in 0..62")
+        m |= 1 << (d // 2)
+    if not m & 1:
+        raise ValueError("a pattern starts at difference 0")
+    return m
+
+
+TWINS = pattern(0, 2)
+TRIPLETS = (pattern(0, 2, 6), pattern(0, 4, 6))
+QUADRUPLETS = pattern(0, 2, 6, 8)
+QUINTUPLETS = (pattern(0, 2, 6, 8, 12), pattern(0, 4, 6, 10, 12))
+SEXTUPLETS = pattern(0, 4, 6, 10, 12, 16)
+CONSTELLATIONS = (TWINS,) + TRIPLETS + (QUADRUPLETS,) + QUINTUPLETS + (SEXTUPLETS,)
+
+
+def _patterns(patterns):
+    """-> (ctypes uint32 array or None, count)"""
+    pats = [int(p) for p in patterns]
+    return ((ctypes.c_uint32 * len(pats))(*pats) if pats else None), len(pats)
+
+
+class Stats:
+    """One dse_stats (include/dse.h): the constellation counts and gap statistics
+    of the odd candidates [g_start, g_start + nbits). ``words`` is the struct as
+    its uint64 words."""
+
+    def __init__(self, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.shape != (_dse.STATS_WORDS,):
+            raise ValueError("a dse_stats is %d uint64 words" % _dse.STATS_WORDS)
+        self.words = w
+
+    @staticmethod
+    def _opt(v):
+        return None if v == _dse.STATS_NONE else v
+
+    g_start = property(lambda s: int(s.words[0]))
+    nbits = property(lambda s: int(s.words[1]))
+    primes = property(lambda s: int(s.words[2]))
+    first_g = property(lambda s: Stats._opt(int(s.words[3])))
+    last_g = property(lambda s: Stats._opt(int(s.words[4])))
+    head = property(lambda s: int(s.words[5]))
+    tail = property(lambda s: int(s.words[6]))
+    gap_overflow = property(lambda s: int(s.words[26]))
+    max_gap = property(lambda s: int(s.words[24]))
+    max_gap_g = property(lambda s: Stats._opt(int(s.words[25])))
+
+    @property
+    def first(self) -> Optional[int]:
+        """The first prime of the range, or None."""
+        return None if self.first_g is None else 3 + 2 * self.first_g
+
+    @property
+    def last(self) -> Optional[int]:
+        return None if self.last_g is None else 3 + 2 * self.last_g
+
+    @property
+    def patterns(self) -> List[int]:
+        return [int(v) for v in self.words[8:8 + int(self.words[7])]]
+
+    @property
+    def matches(self) -> List[int]:
+        """Matches of each pattern, aligned with ``patterns``."""
+        return [int(v) for v in self.words[16:16 + int(self.words[7])]]
+
+    @property
+    def gaps(self) -> np.ndarray:
+        """uint64[1024]: gaps[d] = number of gaps equal to 2d."""
+        return self.words[27:27 + _dse.STATS_GAP_BINS]
+
+    @property
+    def max_gap_prime(self) -> Optional[int]:
+        """The lower prime of the first maximal gap, or None with fewer than two primes."""
+        return None if self.max_gap_g is None else 3 + 2 * self.max_gap_g
+
+    def merge(self, other: "Stats") -> "Stats":
+        """The statistics of this range followed by the adjacent ``other`` (dse_stats_merge)."""
+        out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
+        check(lib().dse_stats_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_stats_merge")
+        return Stats(out)
+
+    def __eq__(self, other):
+        return isinstance(other, Stats) and np.array_equal(self.words, other.words)
+
+    def __repr__(self):
+        return (f"Stats(g_start={self.g_start}, nbits={self.nbits}, primes={self.primes}, matches={self.matches}, "
+                f"max_gap={self.max_gap} at {self.max_gap_prime})")
+
+
+def stats_host(mask: np.ndarray, g_start: int, nbits: int, patterns=CONSTELLATIONS) -> Stats:
+    """Test-only: the statistics kernels' per-word bodies run on the host over a
+    host mask (include/dse.h dse_debug_stats_host)."""
+    pats, n = _patterns(patterns)
+    out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    check(lib().dse_debug_stats_host(u64p(m) if len(m) else None, g_start, nbits, pats, n, u64p(out)),
+          "dse_debug_stats_host")
+    return Stats(out)
+
+
 class Context:
     """A libdse context: one process driving ``num_gpus`` devices, or one
     device (``device=``) for one-process-per-GPU ranks. ``logical=k`` (tests
@@ -202,6 +309,43 @@ class Context:
             return np.empty(0, dtype=np.uint64)
         b = hi if hi & 1 else hi - 1
         return self.primes_range((a - 3) // 2, (b - a) // 2 + 1)
+
+    # -- statistics of a mask -----------------------------------------------------
+    def stats_dev_async(self, g_start: int, nbits: int, mask_ptr: int, patterns, stats_ptr: int,
+                        stream_ptr: int = 0):
+        """The device mask's constellation counts and gap statistics as one
+        dse_stats (_dse.STATS_WORDS uint64 words) in device memory at stats_ptr
+        (include/dse.h dse_stats_dev_async)."""
+        pats, n = _patterns(patterns)
+        check(lib().dse_stats_dev_async(self.ptr, g_start, nbits, mask_ptr or None, pats, n, stats_ptr or None,
+                                        stream_ptr or None),
+              "dse_stats_dev_async")
+
+    def stats_range(self, g_start: int, nbits: int, patterns=CONSTELLATIONS) -> Stats:
+        """gen-table + sieve-e of an odd-index range and its statistics, computed
+        on the device: only the dse_stats reaches the host."""
+        pats, n = _patterns(patterns)
+        out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
+        check(lib().dse_stats_range(self.ptr, g_start, nbits, pats, n, u64p(out)), "dse_stats_range")
+        return Stats(out)
+
+    def resident_stats(self, my_num: Optional[int] = None, patterns=CONSTELLATIONS) -> Stats:
+        """The statistics of a chunk the last sieve_all left on its device, or
+        (my_num=None) of all its chunks: the per-chunk results merged in order."""
+        pats, n = _patterns(patterns)
+        out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
+        check(lib().dse_stats_resident(self.ptr, 0 if my_num is None else my_num, pats, n, u64p(out)),
+              "dse_stats_resident")
+        return Stats(out)
+
+    def stats_window(self, lo: int, hi: int, patterns=CONSTELLATIONS) -> Stats:
+        """The statistics of the odd values in [max(lo, 3), hi] (primes_window's
+        convention); an empty window gives the empty result."""
+        a = max(lo, 3) | 1
+        if hi < a:
+            return self.stats_range(min((a - 3) // 2, 1 << 62), 0, patterns)
+        b = hi if hi & 1 else hi - 1
+        return self.stats_range((a - 3) // 2, (b - a) // 2 + 1, patterns)
 
 
 def base_table_bytes(limit: int) -> int:

@@ -271,6 +271,79 @@ int32_t dse_primes_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, uint64_
 int32_t dse_primes_resident(dse_ctx *ctx, int32_t my_num, uint64_t first,
                             uint64_t *out, uint64_t out_cap, uint64_t *total, uint64_t *written);
 
+/* ---- statistics of a mask ------------------------------------------------- */
+
+/* Constellation counts and prime-gap statistics of a device-resident mask, computed on the GPU in
+ * one read of the mask; only the dse_stats crosses to the host. All statistics are over the odd
+ * primes of the mask (candidate g is the value 3 + 2g): the prime 2 is in no mask and the gap 2 -> 3
+ * is never counted.
+ *
+ * Pattern: a uint32 with bit 0 set. Bit j set means the candidate j places above must be prime too
+ * (the value p + 2j); its span is its bit length (at most 32: differences up to 62). A pattern
+ * matches at g when every required candidate g + j is prime, and a match is counted for a range when
+ * ALL its members lie inside the range; matches across range ends are counted only by
+ * dse_stats_merge. Twins are 0b11, triplets 0b1011 (p, p+2, p+6) and 0b1101 (p, p+4, p+6),
+ * quadruplets 0b11011, quintuplets 0b1011011 and 0b1101101, sextuplets 0b101101101 (primesieve's
+ * conventions: (3,5) and (5,7) are twins, (3,5,7) matches no triplet pattern). The pattern 1 counts
+ * the primes.
+ *
+ * Gap: the difference of two consecutive primes that both lie in the range. gaps[d] = number of
+ * gaps equal to 2d, d < DSE_STATS_GAP_BINS; larger gaps are counted in gap_overflow (synthetic masks
+ * only: every prime gap below 2^64 is under 1600). max_gap is exact whatever its size, max_gap_g the
+ * odd index of the lower prime of the FIRST such gap; with fewer than two primes max_gap = 0 and
+ * max_gap_g = DSE_STATS_NONE.
+ *
+ * Every member is a uint64_t and there is no padding: bindings may treat a dse_stats as an array of
+ * DSE_STATS_WORDS uint64 words. head and tail make two adjacent results mergeable by host
+ * arithmetic alone: the candidates either side of a seam are a.tail (last candidate at bit 63)
+ * followed by b.head (first candidate at bit 0), a 128-bit window with the seam in the middle. */
+#define DSE_STATS_MAX_PATTERNS 8
+#define DSE_STATS_GAP_BINS 1024
+#define DSE_STATS_NONE UINT64_MAX
+#define DSE_STATS_WORDS (27 + DSE_STATS_GAP_BINS)
+typedef struct dse_stats {
+  uint64_t g_start, nbits;      /* the range the numbers are of */
+  uint64_t primes;              /* set bits */
+  uint64_t first_g, last_g;     /* odd index of the first / last prime, DSE_STATS_NONE if none */
+  uint64_t head;                /* bit i = candidate g_start + i, i < min(64, nbits); other bits 0 */
+  uint64_t tail;                /* bit 63 - i = candidate g_start + nbits - 1 - i, i < min(64, nbits); other bits 0 */
+  uint64_t npatterns, pattern[DSE_STATS_MAX_PATTERNS], matches[DSE_STATS_MAX_PATTERNS]; /* unused slots 0 */
+  uint64_t max_gap, max_gap_g, gap_overflow;
+  uint64_t gaps[DSE_STATS_GAP_BINS]; /* gaps[0] stays 0 */
+} dse_stats;
+
+/* Async on stream, on a caller-owned device mask. patterns is a host array of npatterns values,
+ * passed by value into the launch and never retained. stats_dev: sizeof(dse_stats) bytes of device
+ * memory, 8-byte aligned; every member is written and nothing outside it is touched. Bits past
+ * nbits in the last word are ignored; nbits = 0 writes the empty result. DSE_EINVAL for a null ctx
+ * or stats_dev, a null mask with nbits > 0, a misaligned stats_dev, npatterns > 8, null patterns
+ * with npatterns > 0, or a pattern that is 0 or has bit 0 clear. DSE_ERANGE for a range beyond 2^62
+ * or more than 2^44 candidates in one call. */
+int32_t dse_stats_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                            const uint64_t *mask_dev, const uint32_t *patterns, uint32_t npatterns,
+                            dse_stats *stats_dev, void *stream);
+
+/* gen-table + sieve-e + statistics of an odd-index range, on the first device; host result. The
+ * range rules of dse_sieve_odd_range apply. */
+int32_t dse_stats_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                        const uint32_t *patterns, uint32_t npatterns, dse_stats *out);
+
+/* The statistics of chunk my_num left resident by the last dse_sieve_all; my_num = 0: of all P
+ * chunks, that is of [3, 3 + 2 P cs), the candidates the reference's files hold. For all chunks,
+ * every chunk's launches are enqueued on its own device's stream before any is waited for, and the
+ * P results are merged on the host in chunk order. DSE_EINVAL if the chunk is not resident. */
+int32_t dse_stats_resident(dse_ctx *ctx, int32_t my_num,
+                           const uint32_t *patterns, uint32_t npatterns, dse_stats *out);
+
+/* The statistics of the union of two adjacent ranges, by host arithmetic only; out may alias a or
+ * b. Needs a->g_start + a->nbits == b->g_start and equal pattern lists (else DSE_EINVAL; out is not
+ * touched); a union that ends above 2^62 gives DSE_ERANGE. Counts and histograms add; the matches
+ * that straddle the seam are counted from a->tail and b->head; the seam's gap is added when both
+ * sides hold a prime; the maximal gap is taken over a, the seam, then b, keeping the first strictly
+ * greatest; head and tail of the union are rebuilt (either side may be shorter than 64 candidates,
+ * or empty). */
+int32_t dse_stats_merge(const dse_stats *a, const dse_stats *b, dse_stats *out);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -309,6 +382,9 @@ int32_t dse_primes_resident(dse_ctx *ctx, int32_t my_num, uint64_t first,
  *   format slabs of at most k mask words (slab seams on tiny inputs); 0 = default.
  *   "primes_slab_entries" = k > 0: dse_primes_range / dse_primes_resident move
  *   slabs of at most k values (slab seams on tiny inputs); 0 = default.
+ *   "stats_grid" = k in 1..1024: the dse_stats_* launches use at most k
+ *   workgroups, so one workgroup walks several tiles and the closing launch
+ *   sums several slabs on tiny inputs; 0 = default (3 per compute unit).
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -318,7 +394,8 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   "rccl_ranks": ranks of its communicator as ncclCommCount reports (0: none);
  *   "table_local_builds": base tables built on a device of their own instead
  *   of broadcast (one per device and call);
- *   "primes_tile_bits": candidates per tile of the dse_primes_* kernels.
+ *   "primes_tile_bits": candidates per tile of the dse_primes_* kernels;
+ *   "stats_tile_bits": candidates per tile of the dse_stats_* kernels.
  * DSE_EINVAL for an unknown name. */
 int32_t dse_debug_get_stat(dse_ctx *ctx, const char *name, int64_t *value);
 
@@ -359,6 +436,13 @@ int32_t dse_debug_finish_format(uint64_t v, uint32_t flags, char out[32]);
  * rank0 above 2^62. */
 int32_t dse_debug_primes_word(uint64_t word, uint64_t g_word_start, uint64_t rank0, uint64_t first,
                               uint64_t cap, uint64_t out[64]);
+
+/* The dse_stats_* kernels' own per-word bodies, run on the host in a plain loop
+ * over the words of a host mask (no device call): the same result as
+ * dse_stats_dev_async on the same bits. Test-only; DSE_EINVAL / DSE_ERANGE as
+ * dse_stats_dev_async for the mask, the patterns and the range. */
+int32_t dse_debug_stats_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits,
+                             const uint32_t *patterns, uint32_t npatterns, dse_stats *out);
 
 #ifdef __cplusplus
 }
