@@ -16,6 +16,7 @@
 
 #include <algorithm>
 
+#include "dse_block.h"
 #include "dse_internal.h"
 
 namespace dse {
@@ -35,50 +36,30 @@ constexpr uint32_t kCompactStage = 8192;  // LDS slots for a block's primes (32 
 __global__ __launch_bounds__(kCompactThreads) void compact_count_kernel(const uint64_t* __restrict__ mask,
                                                                         uint64_t words,
                                                                         uint32_t* __restrict__ block_sums) {
-  __shared__ uint32_t s_part[kCompactThreads / 64];
+  __shared__ uint32_t s_wave[kCompactThreads / 64];
   const uint64_t w0 = (uint64_t)blockIdx.x * kCompactBlockWords + threadIdx.x * kCompactWordsPerThread;
   uint32_t c = 0;
 #pragma unroll
   for (uint32_t k = 0; k < kCompactWordsPerThread; ++k)
     if (w0 + k < words) c += __popcll(mask[w0 + k]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (uint32_t w = 0; w < kCompactThreads / 64; ++w) t += s_part[w];
-    block_sums[blockIdx.x] = t;
-  }
+  const uint32_t t = block_sum<kCompactThreads>(c, s_wave);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = t;
 }
 
 // exclusive scan of block sums in place; total -> table header count
-__global__ __launch_bounds__(1024) void compact_scan_kernel(uint32_t* __restrict__ block_sums, uint32_t nblocks,
+__global__ __launch_bounds__(kSliceThreads) void compact_scan_kernel(uint32_t* __restrict__ block_sums, uint32_t nblocks,
                                                             void* __restrict__ table, uint32_t cap, uint64_t limit) {
-  __shared__ uint32_t s_scan[1024];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t per = (nblocks + 1023) / 1024;
-  const uint32_t b0 = tid * per, b1 = min(nblocks, b0 + per);
-  uint32_t sum = 0;
-  for (uint32_t b = b0; b < b1; ++b) sum += block_sums[b];
-  s_scan[tid] = sum;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024; o <<= 1) {
-    const uint32_t x = tid >= o ? s_scan[tid - o] : 0;
-    __syncthreads();
-    s_scan[tid] += x;
-    __syncthreads();
-  }
-  uint32_t run = s_scan[tid] - sum;
-  for (uint32_t b = b0; b < b1; ++b) {
+  __shared__ uint32_t s_wave[kSliceThreads / 64];
+  const ScanSlice<uint32_t> s = slice_scan(nblocks, s_wave, [&](uint32_t b) { return block_sums[b]; });
+  uint32_t run = s.start;
+  for (uint32_t b = s.b0; b < s.b1; ++b) {
     const uint32_t v = block_sums[b];
     block_sums[b] = run;
     run += v;
   }
-  if (tid == 1023) {
+  if (threadIdx.x == 0) {
     TableHeader* h = reinterpret_cast<TableHeader*>(table);
-    const uint32_t total = s_scan[1023];
-    h->count = total <= cap ? total : 0xFFFFFFFFu;
+    h->count = s.total <= cap ? s.total : 0xFFFFFFFFu;
     h->cap = cap;
     h->limit = limit;
   }
@@ -88,7 +69,7 @@ __global__ __launch_bounds__(kCompactThreads) void compact_write_kernel(const ui
                                                                         uint64_t words,
                                                                         const uint32_t* __restrict__ block_offs,
                                                                         uint32_t* __restrict__ P, uint32_t cap) {
-  __shared__ uint32_t s_scan[kCompactThreads];
+  __shared__ uint32_t s_wave[kCompactThreads / 64];
   __shared__ uint32_t s_stage[kCompactStage];
   const uint32_t tid = threadIdx.x;
   const uint64_t w0 = (uint64_t)blockIdx.x * kCompactBlockWords + tid * kCompactWordsPerThread;
@@ -99,21 +80,14 @@ __global__ __launch_bounds__(kCompactThreads) void compact_write_kernel(const ui
     v[k] = w0 + k < words ? mask[w0 + k] : 0ull;
     c += __popcll(v[k]);
   }
-  s_scan[tid] = c;
-  __syncthreads();
-  for (uint32_t o = 1; o < kCompactThreads; o <<= 1) {
-    const uint32_t x = tid >= o ? s_scan[tid - o] : 0;
-    __syncthreads();
-    s_scan[tid] += x;
-    __syncthreads();
-  }
+  uint32_t total;
+  uint32_t pos = block_scan<kCompactThreads>(c, s_wave, &total) - c;
   // the block's primes are staged in LDS in order, then stored as one
   // contiguous run (each thread's primes are consecutive slots, so direct
   // stores would put a wave's lanes ~a dozen slots apart: one line each);
   // slots past kCompactStage (never at the densest block, 6,542 primes) go
   // straight to global memory
-  const uint32_t base = block_offs[blockIdx.x], total = s_scan[kCompactThreads - 1];
-  uint32_t pos = s_scan[tid] - c;
+  const uint32_t base = block_offs[blockIdx.x];
 #pragma unroll
   for (uint32_t k = 0; k < kCompactWordsPerThread; ++k) {
     uint64_t x = v[k];
@@ -222,7 +196,7 @@ static hipError_t launch_base_primes(uint64_t limit, void* table, uint32_t cap, 
   hipLaunchKernelGGL(base_mask_kernel, dim3(grid), dim3(kBaseMaskThreads), 0, stream, limit, mask, words, wpw);
   hipLaunchKernelGGL(compact_count_kernel, dim3(nblocks), dim3(kCompactThreads), 0, stream, mask, (uint64_t)words,
                      sums);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, stream, sums, nblocks, table, cap, limit);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kSliceThreads), 0, stream, sums, nblocks, table, cap, limit);
   uint32_t* P = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(table) + 16);
   hipLaunchKernelGGL(compact_write_kernel, dim3(nblocks), dim3(kCompactThreads), 0, stream, mask, (uint64_t)words,
                      sums, P, cap);
@@ -254,7 +228,7 @@ hipError_t launch_base_primes_big(uint64_t limit, void* table, uint32_t cap, int
   e = launch_sieve_range(t0, 0, nb, reinterpret_cast<uint32_t*>(mask), cnt, num_cus, stream, nullptr, nullptr);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(compact_count_kernel, dim3(nblocks), dim3(kCompactThreads), 0, stream, mask, words, sums);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, stream, sums, nblocks, table, cap, limit);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kSliceThreads), 0, stream, sums, nblocks, table, cap, limit);
   uint32_t* P = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(table) + 16);
   hipLaunchKernelGGL(compact_write_kernel, dim3(nblocks), dim3(kCompactThreads), 0, stream, mask, words, sums, P,
                      cap);

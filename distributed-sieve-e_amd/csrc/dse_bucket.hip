@@ -4,6 +4,7 @@
 // format with the wheel kernel (dse_wheel_geometry.h, dse_wheel_args.h) and
 // runs that kernel over each pass through launch_wheel_bucketed
 // (dse_wheel.hip).
+#include "dse_block.h"
 #include "dse_wheel_args.h"
 
 namespace dse {
@@ -229,33 +230,21 @@ __global__ __launch_bounds__(256) void bucket_colscan_kernel(uint32_t* __restric
 // n0[] all 0) and the pass's count gets bit 63 set, so neither an
 // out-of-bounds store nor a silently wrong count can result; the host entry
 // points report it as DSE_EINTERNAL (dse_device_status).
-__global__ __launch_bounds__(1024) void bucket_startscan_kernel(const uint32_t* __restrict__ tot, uint32_t nseg,
+__global__ __launch_bounds__(kSliceThreads) void bucket_startscan_kernel(const uint32_t* __restrict__ tot, uint32_t nseg,
                                                                 uint32_t* __restrict__ start, uint64_t cap,
                                                                 uint32_t* __restrict__ flag,
                                                                 unsigned long long* __restrict__ count) {
-  __shared__ uint32_t s_scan[1024];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t per = (nseg + 1023) / 1024;
-  const uint32_t b0 = tid * per, b1 = min(nseg, b0 + per);
-  uint32_t sum = 0;
-  for (uint32_t b = b0; b < b1; ++b) sum += tot[b];
-  s_scan[tid] = sum;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024; o <<= 1) {
-    const uint32_t x = tid >= o ? s_scan[tid - o] : 0;
-    __syncthreads();
-    s_scan[tid] += x;
-    __syncthreads();
-  }
-  const bool over = s_scan[1023] > cap;  // s_scan[1023]: every thread sees the same total
-  uint32_t run = s_scan[tid] - sum;
-  for (uint32_t b = b0; b < b1; ++b) {
+  __shared__ uint32_t s_wave[kSliceThreads / 64];
+  const ScanSlice<uint32_t> s = slice_scan(nseg, s_wave, [&](uint32_t b) { return tot[b]; });
+  const bool over = s.total > cap;  // every thread sees the same total
+  uint32_t run = s.start;
+  for (uint32_t b = s.b0; b < s.b1; ++b) {
     const uint32_t t = tot[b];
     start[b] = over ? 0u : run;
     run += t;
   }
-  if (tid == 1023) {
-    start[nseg] = over ? 0u : s_scan[1023];
+  if (threadIdx.x == 0) {
+    start[nseg] = over ? 0u : s.total;
     if (over) {
       flag[1] = 1u;  // this pass (read by the kernels below)
       flag[0] = 1u;  // sticky, cleared by dse_device_status
@@ -805,7 +794,7 @@ hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, 
                        ba, range, cols);
     hipLaunchKernelGGL(bucket_colscan_kernel, dim3((uint32_t)((ns + 3) / 4)), dim3(256), 0, stream, cols,
                        (uint32_t)ns, tot);
-    hipLaunchKernelGGL(bucket_startscan_kernel, dim3(1), dim3(1024), 0, stream, tot, (uint32_t)ns, start, cap,
+    hipLaunchKernelGGL(bucket_startscan_kernel, dim3(1), dim3(kSliceThreads), 0, stream, tot, (uint32_t)ns, start, cap,
                        scratch->flag, count);
     const uint32_t nsup = (uint32_t)((ns + kSupSegs - 1) >> kSupLog);
     const uint32_t nfill = band0 ? kBucketGrid : 0;

@@ -5,7 +5,7 @@
 // mask becomes the file's text in HBM, so only text leaves the GPU. Three
 // launches on the caller's stream, the ordered count / scan / write shape of
 // the base-prime compaction (dse_base.hip):
-//   finish_size_kernel  per tile of kFinTileWords mask words: entries and the
+//   finish_size_kernel  per tile of kMaskTileWords mask words: entries and the
 //                       bytes of their printed values ("value bytes");
 //   finish_scan_kernel  one workgroup: 64-bit exclusive scan of the tile pairs
 //                       in place, and the call's totals;
@@ -18,38 +18,36 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dse_block.h"
 #include "dse_finish_fmt.h"
 #include "dse_internal.h"
 
 namespace dse {
 namespace {
 
-constexpr uint32_t kFinThreads = 256;
-constexpr uint32_t kFinTileWords = kFinThreads;  // one mask word per thread
+constexpr uint32_t kFinThreads = kMaskTileWords;  // one mask word per thread
+constexpr uint32_t kFinWaves = kFinThreads / 64;
 // LDS window of a tile's text. A tile of a prime mask near 1e9 prints about
 // 19 KB; an all-ones tile of 19-digit values prints 344 KB and takes 11 windows.
 constexpr uint32_t kFinWindow = 32768;
 
 struct FinArgs {
-  const uint64_t* mask;
-  uint64_t g_start, nbits, words, first_rank;
+  MaskRange r;
+  uint64_t first_rank;
   uint32_t flags;
 };
 
-// Word w of the range as the entries it prints: bits past nbits dropped; with
-// the hack, bits 0..3 of word 0 are the four literal entries whatever the mask holds.
+// Word w of the range as the entries it prints: with the hack, bits 0..3 of
+// word 0 are the four literal entries whatever the mask holds.
 __device__ __forceinline__ uint64_t fin_load_word(const FinArgs& a, uint64_t w) {
-  if (w >= a.words) return 0ull;
-  uint64_t b = a.mask[w];
-  if (w == a.words - 1 && (a.nbits & 63)) b &= (1ull << (a.nbits & 63)) - 1;
-  if (w == 0 && (a.flags & kFinishHack)) b |= 0xFull;
-  return b;
+  const uint64_t b = mask_word(a.r, w);
+  return w == 0 && (a.flags & kFinishHack) ? b | 0xFull : b;
 }
 
 // value printed for bit b of word w
 __device__ __forceinline__ uint64_t fin_value(const FinArgs& a, uint64_t w, uint32_t b) {
   if (w == 0 && b < 4 && (a.flags & kFinishHack)) return b == 0 ? 2ull : 2ull * b + 1ull;  // 2 3 5 7
-  return 3ull + 2ull * (a.g_start + w * 64ull + b);
+  return 3ull + 2ull * (a.r.g_start + w * 64ull + b);
 }
 
 // entries and value bytes of one word, packed (entries << 32 | bytes): the
@@ -71,26 +69,11 @@ __device__ __forceinline__ uint64_t fin_word_cost(const FinArgs& a, uint64_t w, 
   return ((uint64_t)c << 32) | d;
 }
 
-// inclusive scan of one uint64 per thread over the workgroup (N threads)
-template <uint32_t N>
-__device__ __forceinline__ uint64_t fin_block_scan(uint64_t v, uint64_t* s) {
-  const uint32_t tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (uint32_t o = 1; o < N; o <<= 1) {
-    const uint64_t x = tid >= o ? s[tid - o] : 0ull;
-    __syncthreads();
-    s[tid] += x;
-    __syncthreads();
-  }
-  return s[tid];
-}
-
 __global__ __launch_bounds__(kFinThreads) void finish_size_kernel(FinArgs a, unsigned long long* __restrict__ sums) {
-  __shared__ uint64_t s_scan[kFinThreads];
-  const uint64_t w = (uint64_t)blockIdx.x * kFinTileWords + threadIdx.x;
-  const uint64_t t = fin_block_scan<kFinThreads>(fin_word_cost(a, w, fin_load_word(a, w)), s_scan);
-  if (threadIdx.x == kFinThreads - 1) {
+  __shared__ uint64_t s_wave[kFinWaves];
+  const uint64_t w = (uint64_t)blockIdx.x * kMaskTileWords + threadIdx.x;
+  const uint64_t t = block_sum<kFinThreads>(fin_word_cost(a, w, fin_load_word(a, w)), s_wave);
+  if (threadIdx.x == 0) {
     sums[2ull * blockIdx.x] = t >> 32;
     sums[2ull * blockIdx.x + 1] = t & 0xFFFFFFFFull;
   }
@@ -99,39 +82,22 @@ __global__ __launch_bounds__(kFinThreads) void finish_size_kernel(FinArgs a, uns
 // exclusive scan of the (entries, value bytes) pairs in place; totals[0] =
 // entries, totals[1] = text bytes of the slice, the closing "\n" of a partial
 // last line included
-__global__ __launch_bounds__(1024) void finish_scan_kernel(unsigned long long* __restrict__ sums, uint32_t ntiles,
+__global__ __launch_bounds__(kSliceThreads) void finish_scan_kernel(unsigned long long* __restrict__ sums, uint32_t ntiles,
                                                            uint64_t first_rank, uint32_t flags,
                                                            unsigned long long* __restrict__ totals) {
-  __shared__ uint64_t s_c[1024];
-  __shared__ uint64_t s_d[1024];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t per = (ntiles + 1023) / 1024;
-  const uint32_t b0 = min(ntiles, tid * per), b1 = min(ntiles, b0 + per);
-  uint64_t c = 0, d = 0;
-  for (uint32_t b = b0; b < b1; ++b) {
-    c += sums[2ull * b];
-    d += sums[2ull * b + 1];
-  }
-  s_c[tid] = c;
-  s_d[tid] = d;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024; o <<= 1) {
-    const uint64_t xc = tid >= o ? s_c[tid - o] : 0ull, xd = tid >= o ? s_d[tid - o] : 0ull;
-    __syncthreads();
-    s_c[tid] += xc;
-    s_d[tid] += xd;
-    __syncthreads();
-  }
-  uint64_t rc = s_c[tid] - c, rd = s_d[tid] - d;
-  for (uint32_t b = b0; b < b1; ++b) {
+  __shared__ uint64_t s_wave[2][kSliceThreads / 64];
+  const ScanSlice<uint64_t> c = slice_scan(ntiles, s_wave[0], [&](uint32_t b) { return sums[2ull * b]; });
+  const ScanSlice<uint64_t> d = slice_scan(ntiles, s_wave[1], [&](uint32_t b) { return sums[2ull * b + 1]; });
+  uint64_t rc = c.start, rd = d.start;
+  for (uint32_t b = c.b0; b < c.b1; ++b) {
     const uint64_t vc = sums[2ull * b], vd = sums[2ull * b + 1];
     sums[2ull * b] = rc;
     sums[2ull * b + 1] = rd;
     rc += vc;
     rd += vd;
   }
-  if (tid == 1023) {
-    const uint64_t C = s_c[1023], D = s_d[1023], end = first_rank + C;
+  if (threadIdx.x == 0) {
+    const uint64_t C = c.total, D = d.total, end = first_rank + C;
     const uint64_t closing = ((flags & kFinishLast) && end % 10u) ? 1u : 0u;
     totals[0] = C;
     totals[1] = D + fin_sep_bytes(end) - fin_sep_bytes(first_rank) + closing;
@@ -153,7 +119,7 @@ __global__ __launch_bounds__(kFinThreads) void finish_emit_kernel(FinArgs a,
                                                                   const unsigned long long* __restrict__ sums,
                                                                   const unsigned long long* __restrict__ totals,
                                                                   char* __restrict__ text, uint64_t text_cap) {
-  __shared__ uint64_t s_scan[kFinThreads];
+  __shared__ uint64_t s_wave[kFinWaves];
   __shared__ __attribute__((aligned(16))) char s_text[kFinWindow];
   const uint64_t total_bytes = totals[1];
   if (total_bytes > text_cap) return;  // the text does not fit: not one byte is written
@@ -161,13 +127,13 @@ __global__ __launch_bounds__(kFinThreads) void finish_emit_kernel(FinArgs a,
   const bool dbl = a.flags & kFinishDoubles;
   if (blockIdx.x == 0 && tid == 0 && (a.flags & kFinishLast) && (a.first_rank + totals[0]) % 10u)
     text[total_bytes - 1] = '\n';  // closes the file's partial last line
-  if (a.words == 0) return;
+  if (a.r.words == 0) return;
 
-  const uint64_t w = (uint64_t)blockIdx.x * kFinTileWords + tid;
+  const uint64_t w = (uint64_t)blockIdx.x * kMaskTileWords + tid;
   uint64_t bits = fin_load_word(a, w);
   const uint64_t cost = fin_word_cost(a, w, bits);
-  const uint64_t incl = fin_block_scan<kFinThreads>(cost, s_scan);
-  const uint64_t tile = s_scan[kFinThreads - 1], excl = incl - cost;
+  uint64_t tile;
+  const uint64_t excl = block_scan<kFinThreads>(cost, s_wave, &tile) - cost;
 
   // the tile's first rank and first byte, and this word's
   const uint64_t R_t = a.first_rank + sums[2ull * blockIdx.x];
@@ -217,27 +183,19 @@ __global__ __launch_bounds__(kFinThreads) void finish_emit_kernel(FinArgs a,
 }  // namespace
 
 uint64_t finish_scratch_bytes(uint64_t nbits) {
-  const uint64_t words = (nbits + 63) / 64;
-  const uint64_t ntiles = (words + kFinTileWords - 1) / kFinTileWords;
+  const uint64_t ntiles = mask_tiles(nbits);
   return (ntiles ? ntiles : 1) * 2 * sizeof(unsigned long long);
 }
 
 hipError_t launch_finish_text(uint32_t flags, uint64_t g_start, uint64_t nbits, const uint64_t* mask,
                               uint64_t first_rank, void* text, uint64_t text_cap, unsigned long long* totals,
                               void* tile_sums, hipStream_t stream) {
-  FinArgs a;
-  a.mask = mask;
-  a.g_start = g_start;
-  a.nbits = nbits;
-  a.words = (nbits + 63) / 64;
-  a.first_rank = first_rank;
-  a.flags = flags;
-  const uint64_t ntiles64 = (a.words + kFinTileWords - 1) / kFinTileWords;
-  if (ntiles64 > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  const uint32_t ntiles = (uint32_t)ntiles64;
+  const FinArgs a{mask_range(mask, g_start, nbits), first_rank, flags};
+  if (mask_tiles(nbits) > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  const uint32_t ntiles = (uint32_t)mask_tiles(nbits);
   unsigned long long* sums = reinterpret_cast<unsigned long long*>(tile_sums);
   if (ntiles) hipLaunchKernelGGL(finish_size_kernel, dim3(ntiles), dim3(kFinThreads), 0, stream, a, sums);
-  hipLaunchKernelGGL(finish_scan_kernel, dim3(1), dim3(1024), 0, stream, sums, ntiles, first_rank, flags, totals);
+  hipLaunchKernelGGL(finish_scan_kernel, dim3(1), dim3(kSliceThreads), 0, stream, sums, ntiles, first_rank, flags, totals);
   // an empty range still closes a partial line (block 0)
   hipLaunchKernelGGL(finish_emit_kernel, dim3(ntiles ? ntiles : 1), dim3(kFinThreads), 0, stream, a, sums, totals,
                      reinterpret_cast<char*>(text), text_cap);

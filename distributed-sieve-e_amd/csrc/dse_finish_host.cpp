@@ -117,19 +117,16 @@ extern "C" int32_t dse_write_primes_file(const char* path, int32_t my_num, int64
 namespace {
 
 constexpr uint32_t kFinishFlagsAll = DSE_FINISH_DOUBLES | DSE_FINISH_HACK | DSE_FINISH_LAST;
-constexpr uint64_t kFinishBufMax = 64ull << 20;  // 4 buffers: 256 MiB per device in all
-constexpr uint64_t kFinishBufMin = 1ull << 20;
 
 // what both the async entry point and the file entry points refuse
 int32_t finish_check_range(uint32_t flags, uint64_t g_start, uint64_t nbits) {
   if (flags & ~kFinishFlagsAll) return fail(DSE_EINVAL, "unknown finish flag");
   if ((flags & DSE_FINISH_HACK) && nbits < 4)
     return fail(DSE_EINVAL, "finish's 2/3/5/7 hack needs a chunk of >= 4 candidates");
-  if (int32_t rc = check_odd_range(g_start, nbits)) return rc;
+  if (int32_t rc = check_odd_range(g_start, nbits)) return rc;  // bounds the next line's arithmetic
   if ((flags & DSE_FINISH_DOUBLES) && nbits && 3 + 2 * (g_start + nbits - 1) >= (1ull << 53))
     return fail(DSE_ERANGE, "Double printing needs every value below 2^53");
-  if (nbits > (1ull << 44)) return fail(DSE_ERANGE, "finish range above 2^44 candidates in one call");
-  return DSE_OK;
+  return check_mask_range("finish", g_start, nbits);
 }
 
 // The three launches on `stream`, with the context's tile-sum scratch ordered
@@ -137,42 +134,14 @@ int32_t finish_check_range(uint32_t flags, uint64_t g_start, uint64_t nbits) {
 int32_t finish_launch(DevState& d, uint32_t flags, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
                       uint64_t first_rank, void* text_dev, uint64_t text_cap, unsigned long long* totals_dev,
                       hipStream_t stream) {
-  StreamScratch& sums = d.fin.sums;
-  // a grow takes half as much again, 64 KiB at least
-  const uint64_t need = finish_scratch_bytes(nbits);
-  HIP_TRY(acquire_scratch(&sums, sums.buf.bytes >= need ? need : std::max<uint64_t>(need + need / 2, 1ull << 16),
-                          stream));
+  StreamScratch& sums = d.finish_sums;
+  HIP_TRY(acquire_scratch_roomy(&sums, finish_scratch_bytes(nbits), stream));
   const hipError_t e = launch_finish_text(flags, g_start, nbits, mask_dev, first_rank, text_dev, text_cap,
                                           totals_dev, sums.buf.ptr, stream);
   HIP_TRY(release_scratch(&sums, stream));  // also after a failure: what was launched may read the scratch
   if (e != hipSuccess) return fail(DSE_EHIP, std::string("launch_finish_text failed: ") + hipGetErrorString(e));
   return DSE_OK;
 }
-
-}  // namespace
-
-int32_t dse::ensure_finish_bufs(DevState& d, uint64_t want) {
-  FinishState& f = d.fin;
-  if (!f.copy) HIP_TRY(hipStreamCreateWithFlags(&f.copy, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    if (!f.fmt_ev[i]) HIP_TRY(hipEventCreateWithFlags(&f.fmt_ev[i], hipEventDisableTiming));
-    if (!f.copy_ev[i]) HIP_TRY(hipEventCreateWithFlags(&f.copy_ev[i], hipEventDisableTiming));
-  }
-  if (!f.dtotals) HIP_TRY(hipMalloc(&f.dtotals, 4 * sizeof(unsigned long long)));
-  if (!f.htotals) HIP_TRY(hipHostMalloc(&f.htotals, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-  want = std::min(std::max(want, kFinishBufMin), kFinishBufMax);
-  if (f.buf_bytes >= want) return DSE_OK;
-  // every earlier call has drained both streams before it returned
-  f.buf_bytes = 0;
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(grow_buf(&f.dtext[i], want));
-    HIP_TRY(grow_buf(&f.htext[i], want));
-  }
-  f.buf_bytes = want;
-  return DSE_OK;
-}
-
-namespace {
 
 // The slab pipeline: mask_dev (ready in d.stream's order) -> file. Slab i+1 is
 // formatted on d.stream while slab i's text is copied on the copy stream and
@@ -185,31 +154,29 @@ int32_t finish_pipeline(dse_ctx* ctx, DevState& d, FILE* fp, const char* path, u
   if (count_out) *count_out = 0;
   if (!words) return DSE_OK;  // no entries: an empty file
   int32_t rc;
-  if ((rc = ensure_finish_bufs(d, dse_finish_text_bound(g_start, nbits, nbits, flags)))) return rc;
-  FinishState& f = d.fin;
+  if ((rc = ensure_slab_pipe(d, dse_finish_text_bound(g_start, nbits, nbits, flags)))) return rc;
+  SlabPipe& f = d.pipe;
   const uint64_t B = f.buf_bytes;
   const uint64_t cap_words = ctx->finish_slab_words ? ctx->finish_slab_words : ~0ull;
   uint64_t rank = 0;
-  bool copy_pending[2] = {false, false};
 
   auto launch = [&](int slot, uint64_t w0, uint64_t nw) -> int32_t {
     uint32_t fl = flags & DSE_FINISH_DOUBLES;
     if (w0 == 0) fl |= flags & DSE_FINISH_HACK;
     if (w0 + nw == words) fl |= DSE_FINISH_LAST;
     const uint64_t nb = std::min<uint64_t>(nbits - w0 * 64, nw * 64);
-    // the slot's device buffer is free once the copy of the slab that used it has run
-    if (copy_pending[slot]) HIP_TRY(hipStreamWaitEvent(d.stream, f.copy_ev[slot], 0));
-    int32_t r = finish_launch(d, fl, g_start + w0 * 64, nb, mask_dev + w0, rank, f.dtext[slot].ptr, B,
-                              f.dtotals + 2 * slot, d.stream);
-    if (r) return r;
+    int32_t r;
+    if ((r = slab_reuse(f, slot, d.stream))) return r;
+    if ((r = finish_launch(d, fl, g_start + w0 * 64, nb, mask_dev + w0, rank, f.dbuf[slot].ptr, B,
+                           f.dtotals + 2 * slot, d.stream)))
+      return r;
     HIP_TRY(hipMemcpyAsync(f.htotals + 2 * slot, f.dtotals + 2 * slot, 2 * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipEventRecord(f.fmt_ev[slot], d.stream));
     return DSE_OK;
   };
   auto write_slab = [&](int slot, uint64_t bytes) -> int32_t {  // once its copy has run
-    HIP_TRY(hipEventSynchronize(f.copy_ev[slot]));
-    if (bytes && std::fwrite(f.htext[slot].ptr, 1, bytes, fp) != bytes)
+    if (int32_t r = slab_wait(f, slot)) return r;
+    if (bytes && std::fwrite(f.hbuf[slot].ptr, 1, bytes, fp) != bytes)
       return fail(DSE_EIO, std::string("write failed: ") + path);
     return DSE_OK;
   };
@@ -222,7 +189,7 @@ int32_t finish_pipeline(dse_ctx* ctx, DevState& d, FILE* fp, const char* path, u
     uint64_t nw = std::min(std::min(words, cap_words), std::max<uint64_t>(B / 128, 1));
     if ((r = launch(slot, w0, nw))) return r;
     for (;;) {
-      HIP_TRY(hipEventSynchronize(f.fmt_ev[slot]));
+      HIP_TRY(hipStreamSynchronize(d.stream));  // the slab's launch is the stream's last work: its totals
       const uint64_t cnt = f.htotals[2 * slot], bytes = f.htotals[2 * slot + 1];
       if (bytes > B) {  // nothing was written: split the slab and format it again
         if (nw == 1) return fail(DSE_EINTERNAL, "finish: one mask word exceeds the text buffer");
@@ -230,10 +197,7 @@ int32_t finish_pipeline(dse_ctx* ctx, DevState& d, FILE* fp, const char* path, u
         if ((r = launch(slot, w0, nw))) return r;
         continue;
       }
-      HIP_TRY(hipStreamWaitEvent(f.copy, f.fmt_ev[slot], 0));
-      if (bytes) HIP_TRY(hipMemcpyAsync(f.htext[slot].ptr, f.dtext[slot].ptr, bytes, hipMemcpyDeviceToHost, f.copy));
-      HIP_TRY(hipEventRecord(f.copy_ev[slot], f.copy));
-      copy_pending[slot] = true;
+      if ((r = slab_send(f, slot, bytes, d.stream))) return r;
       rank += cnt;
       const uint64_t w_next = w0 + nw;
       const bool more = w_next < words;
@@ -255,9 +219,8 @@ int32_t finish_pipeline(dse_ctx* ctx, DevState& d, FILE* fp, const char* path, u
     return write_slab(prev_slot, prev_bytes);
   };
   rc = run();
-  if (rc) {  // leave nothing in flight on the buffers
-    (void)hipStreamSynchronize(d.stream);
-    (void)hipStreamSynchronize(f.copy);
+  if (rc) {
+    slab_drain(f, d.stream);
     return rc;
   }
   if (count_out) *count_out = rank - ((flags & DSE_FINISH_HACK) ? 4 : 0);
@@ -274,21 +237,6 @@ int32_t finish_close(FILE* fp, const char* path, int32_t rc) {
 }
 
 }  // namespace
-
-void dse::free_finish(FinishState& f) {
-  (void)free_scratch(&f.sums);
-  if (f.copy) (void)hipStreamSynchronize(f.copy);
-  for (int i = 0; i < 2; ++i) {
-    (void)free_buf(&f.dtext[i]);
-    (void)free_buf(&f.htext[i]);
-    if (f.fmt_ev[i]) (void)hipEventDestroy(f.fmt_ev[i]);
-    if (f.copy_ev[i]) (void)hipEventDestroy(f.copy_ev[i]);
-  }
-  if (f.dtotals) (void)hipFree(f.dtotals);
-  if (f.htotals) (void)hipHostFree(f.htotals);
-  if (f.copy) (void)hipStreamDestroy(f.copy);
-  f = FinishState();
-}
 
 extern "C" uint64_t dse_finish_text_bound(uint64_t g_start, uint64_t nbits, uint64_t count, uint32_t flags) {
   // every entry: ", " and a value no longer than the range's largest (the

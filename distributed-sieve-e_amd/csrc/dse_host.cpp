@@ -1,7 +1,9 @@
 // dse_host.cpp -- C-ABI host layer of libdse.so (include/dse.h): contexts,
 // chunk geometry, the base table and its sharing, collectives, the sieve entry
-// points, debug options and stats. The finish side is dse_finish_host.cpp,
-// primes as numbers dse_primes_host.cpp.
+// points, debug options and stats, and what the other host units share (range
+// checks, scratch growth, the two-slot slab pipe). The finish side is
+// dse_finish_host.cpp, primes as numbers dse_primes_host.cpp, statistics
+// dse_stats_host.cpp.
 //
 // Replaces the reference's orchestration of the hot path:
 //   spread-work (sieve.clj:15-34)            -> dse_spread_work (exact int64)
@@ -62,6 +64,10 @@ hipError_t acquire_scratch(StreamScratch* s, uint64_t bytes, hipStream_t stream)
   return s->used ? hipStreamWaitEvent(stream, s->done, 0) : hipSuccess;
 }
 
+hipError_t acquire_scratch_roomy(StreamScratch* s, uint64_t need, hipStream_t stream) {
+  return acquire_scratch(s, s->buf.bytes >= need ? need : std::max<uint64_t>(need + need / 2, 1ull << 16), stream);
+}
+
 hipError_t release_scratch(StreamScratch* s, hipStream_t stream) {
   const hipError_t e = hipEventRecord(s->done, stream);
   if (e == hipSuccess) s->used = true;
@@ -92,6 +98,12 @@ int32_t check_odd_range(uint64_t g_start, uint64_t nbits) {
   return DSE_OK;
 }
 
+int32_t check_mask_range(const char* what, uint64_t g_start, uint64_t nbits) {
+  if (int32_t rc = check_odd_range(g_start, nbits)) return rc;
+  if (nbits > (1ull << 44)) return fail(DSE_ERANGE, std::string(what) + " range above 2^44 candidates in one call");
+  return DSE_OK;
+}
+
 int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mask) {
   const ResidentSet& r = ctx->resident;
   if (!r.valid || my_num < 1 || my_num > r.P)
@@ -99,6 +111,66 @@ int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mas
   *d = &ctx->devs[(size_t)(my_num - 1) % ctx->devs.size()];
   *mask = r.masks[my_num - 1].as<uint64_t>();
   return DSE_OK;
+}
+
+int32_t ensure_slab_pipe(DevState& d, uint64_t want) {
+  SlabPipe& p = d.pipe;
+  if (!p.copy) HIP_TRY(hipStreamCreateWithFlags(&p.copy, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    if (!p.ready_ev[i]) HIP_TRY(hipEventCreateWithFlags(&p.ready_ev[i], hipEventDisableTiming));
+    if (!p.copy_ev[i]) HIP_TRY(hipEventCreateWithFlags(&p.copy_ev[i], hipEventDisableTiming));
+    p.pending[i] = false;  // every earlier call has drained both streams before it returned
+  }
+  if (!p.dtotals) HIP_TRY(hipMalloc(&p.dtotals, 4 * sizeof(unsigned long long)));
+  if (!p.htotals) HIP_TRY(hipHostMalloc(&p.htotals, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+  want = std::min(std::max(want, kSlabBufMin), kSlabBufMax);
+  if (p.buf_bytes >= want) return DSE_OK;
+  p.buf_bytes = 0;
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(grow_buf(&p.dbuf[i], want));
+    HIP_TRY(grow_buf(&p.hbuf[i], want));
+  }
+  p.buf_bytes = want;
+  return DSE_OK;
+}
+
+int32_t slab_reuse(SlabPipe& p, int s, hipStream_t producer) {
+  if (p.pending[s]) HIP_TRY(hipStreamWaitEvent(producer, p.copy_ev[s], 0));
+  return DSE_OK;
+}
+
+int32_t slab_send(SlabPipe& p, int s, uint64_t bytes, hipStream_t producer) {
+  HIP_TRY(hipEventRecord(p.ready_ev[s], producer));
+  HIP_TRY(hipStreamWaitEvent(p.copy, p.ready_ev[s], 0));
+  if (bytes) HIP_TRY(hipMemcpyAsync(p.hbuf[s].ptr, p.dbuf[s].ptr, bytes, hipMemcpyDeviceToHost, p.copy));
+  HIP_TRY(hipEventRecord(p.copy_ev[s], p.copy));
+  p.pending[s] = true;
+  return DSE_OK;
+}
+
+int32_t slab_wait(SlabPipe& p, int s) {
+  HIP_TRY(hipEventSynchronize(p.copy_ev[s]));
+  p.pending[s] = false;
+  return DSE_OK;
+}
+
+void slab_drain(SlabPipe& p, hipStream_t producer) {
+  (void)hipStreamSynchronize(producer);
+  if (p.copy) (void)hipStreamSynchronize(p.copy);
+}
+
+void free_slab_pipe(SlabPipe& p) {
+  if (p.copy) (void)hipStreamSynchronize(p.copy);
+  for (int i = 0; i < 2; ++i) {
+    (void)free_buf(&p.dbuf[i]);
+    (void)free_buf(&p.hbuf[i]);
+    if (p.ready_ev[i]) (void)hipEventDestroy(p.ready_ev[i]);
+    if (p.copy_ev[i]) (void)hipEventDestroy(p.copy_ev[i]);
+  }
+  if (p.dtotals) (void)hipFree(p.dtotals);
+  if (p.htotals) (void)hipHostFree(p.htotals);
+  if (p.copy) (void)hipStreamDestroy(p.copy);
+  p = SlabPipe();
 }
 
 }  // namespace dse
@@ -493,7 +565,8 @@ void dse_destroy(dse_ctx* ctx) {
     (void)free_buf(&d.scratch_mask);
     (void)free_scratch(&d.scratch);
     if (d.scratch.flag) (void)hipFree(d.scratch.flag);
-    free_finish(d.fin);
+    free_slab_pipe(d.pipe);
+    (void)free_scratch(&d.finish_sums);
     (void)free_scratch(&d.primes_sums);
     (void)free_scratch(&d.stats_scratch);
     if (d.xev) (void)hipEventDestroy(d.xev);
@@ -753,9 +826,9 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     if (!ctx->comms.empty()) NCCL_TRY(ncclCommCount(ctx->comms[0], &c));
     *value = c;
   } else if (n == "primes_tile_bits") {
-    *value = (int64_t)kPrimesTileBits;
+    *value = (int64_t)kMaskTileBits;
   } else if (n == "stats_tile_bits") {
-    *value = (int64_t)kStatsTileBits;
+    *value = (int64_t)kMaskTileBits;
   } else {
     return fail(DSE_EINVAL, "unknown stat " + n);
   }

@@ -32,20 +32,26 @@ int32_t fail(int32_t code, const std::string& msg);
       return dse::fail(DSE_ENCCL, std::string(#expr " failed: ") + ncclGetErrorString(r_));    \
   } while (0)
 
-// Device finish (dse_finish.hip): the tile-sum scratch of the three launches
-// (`done` recorded after the emit launch), and the slab pipeline of the file
-// entry points: two device and two pinned host text buffers of `buf_bytes`
-// each (at most kFinishBufMax), grown on demand.
-struct FinishState {
-  StreamScratch sums;
-  Buf dtext[2];
-  Buf htext[2] = {{nullptr, 0, true}, {nullptr, 0, true}};
-  uint64_t buf_bytes = 0;                 // all four text buffers hold this much
-  unsigned long long* dtotals = nullptr;  // device [2][2]
+// The two-slot slab pipe of the blocking entry points that bring a device
+// result to the host in slabs (finish text, prime values): slab i + 1 is
+// produced on the device's stream into slot (i + 1) & 1 while slab i is copied
+// to pinned memory on the copy stream and slab i - 1 is consumed by the
+// calling thread. Two device and two pinned buffers of `buf_bytes` each (1 MiB
+// to 64 MiB, grown on demand) and the events that order them, which only the
+// slab_* operations below touch. A call that uses the pipe drains both streams
+// before it returns.
+constexpr uint64_t kSlabBufMax = 64ull << 20;  // 4 buffers: 256 MiB per device in all
+constexpr uint64_t kSlabBufMin = 1ull << 20;
+struct SlabPipe {
+  Buf dbuf[2];
+  Buf hbuf[2] = {{nullptr, 0, true}, {nullptr, 0, true}};
+  uint64_t buf_bytes = 0;                 // all four buffers hold this much
+  unsigned long long* dtotals = nullptr;  // device [2][2]: a producer's totals, per slot
   unsigned long long* htotals = nullptr;  // pinned [2][2]
-  hipStream_t copy = nullptr;             // the text's D2H copies
-  hipEvent_t fmt_ev[2] = {nullptr, nullptr};
-  hipEvent_t copy_ev[2] = {nullptr, nullptr};
+  hipStream_t copy = nullptr;             // the slabs' D2H copies
+  hipEvent_t ready_ev[2] = {nullptr, nullptr};  // slot produced (producing stream)
+  hipEvent_t copy_ev[2] = {nullptr, nullptr};   // slot copied (copy stream)
+  bool pending[2] = {false, false};             // copy_ev recorded and not yet waited for on the host
 };
 
 struct DevState {
@@ -56,7 +62,8 @@ struct DevState {
   Buf counts;                // device scratch (unsigned long long)
   Buf scratch_mask;          // for dse_sieve_chunk
   Scratch scratch;           // bucketed-pass scratch (high-offset ranges)
-  FinishState fin;           // device finish: scratch and slab buffers
+  SlabPipe pipe;             // slabs to the host: finish text, prime values
+  StreamScratch finish_sums; // device finish (dse_finish.hip): tile-sum scratch of the three launches
   StreamScratch primes_sums; // primes as numbers (dse_primes.hip): tile-sum scratch of the three launches
   StreamScratch stats_scratch; // statistics (dse_stats.hip): the workgroups' slabs, and results on their way to the host
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
@@ -104,16 +111,27 @@ namespace dse {
 // cs = candidates per chunk of (n, P); nums = the odd candidates 3..n
 int32_t chunk_geometry(int64_t n, int32_t P, int64_t* cs, int64_t* nums = nullptr);
 int32_t check_odd_range(uint64_t g_start, uint64_t nbits);
+// check_odd_range, and at most 2^44 candidates: what every consumer of a resident mask refuses
+// ("<what> range above 2^44 candidates in one call")
+int32_t check_mask_range(const char* what, uint64_t g_start, uint64_t nbits);
 // keep_dev: sieve into d.scratch_mask even without a host mask (dse_finish_range_file)
 int32_t sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t nbits, uint64_t* mask_or_null,
                          uint64_t* count, bool keep_dev = false);
 // The device and mask of resident chunk my_num; DSE_EINVAL when it is not resident.
 int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mask);
-void free_finish(FinishState& f);  // dse_finish_host.cpp; the state's device current
-// The slab pipeline's streams, events, totals and its four buffers of min(max(want, 1 MiB), 64 MiB)
-// bytes each (d.fin, grown on demand; dse_finish_host.cpp). dse_primes_host.cpp moves its values
-// through the same buffers: a blocking entry point drains both streams before it returns.
-int32_t ensure_finish_bufs(DevState& d, uint64_t want);
+// The slab pipe (d.pipe; dse_host.cpp), the device current. ensure_slab_pipe: its stream, events,
+// totals and four buffers of min(max(want, 1 MiB), 64 MiB) bytes each, no slot pending.
+int32_t ensure_slab_pipe(DevState& d, uint64_t want);
+void free_slab_pipe(SlabPipe& p);
+// Slot s may be overwritten by work enqueued on `producer` from here on.
+int32_t slab_reuse(SlabPipe& p, int s, hipStream_t producer);
+// What `producer` has enqueued so far fills slot s: its first `bytes` bytes go to the slot's
+// pinned buffer on the copy stream.
+int32_t slab_send(SlabPipe& p, int s, uint64_t bytes, hipStream_t producer);
+// Blocks until the bytes of slab_send(s) are in the slot's pinned buffer.
+int32_t slab_wait(SlabPipe& p, int s);
+// After an error: leaves nothing in flight on the buffers.
+void slab_drain(SlabPipe& p, hipStream_t producer);
 
 }  // namespace dse
 #pragma GCC visibility pop

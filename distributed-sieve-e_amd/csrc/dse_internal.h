@@ -2,10 +2,14 @@
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
 // dse_primes.hip, dse_stats.hip) and the C-ABI host layer (dse_host.cpp,
 // dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp). Not installed;
-// include/dse.h is the ABI.
+// include/dse.h is the ABI. The units that read a resident mask (finish,
+// primes, stats) share its range, tiles and clipped word load (dse_mask.h);
+// every unit with a workgroup sum or scan takes it from dse_block.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "dse_mask.h"
 
 namespace dse {
 
@@ -106,6 +110,8 @@ struct StreamScratch {
   bool used = false;          // `done` has been recorded since the last grow
 };
 hipError_t acquire_scratch(StreamScratch* s, uint64_t bytes, hipStream_t stream);
+// acquire_scratch for at least `need` bytes: a buffer that has to grow takes half as much again, 64 KiB at least
+hipError_t acquire_scratch_roomy(StreamScratch* s, uint64_t need, hipStream_t stream);
 hipError_t release_scratch(StreamScratch* s, hipStream_t stream);
 hipError_t free_scratch(StreamScratch* s);
 
@@ -193,7 +199,7 @@ hipError_t launch_finish_text(uint32_t flags, uint64_t g_start, uint64_t nbits, 
 
 // Primes as numbers (dse_primes.hip): the set bits of mask (odd indices
 // [g_start, g_start + nbits), 64-bit words) as uint64 values 3 + 2 (g_start +
-// bit), ranked in increasing order. A tile is kPrimesTileBits candidates.
+// bit), ranked in increasing order. A tile is kMaskTileBits candidates.
 // launch_primes_scan: the size and scan launches. tile_sums
 // (primes_scratch_bytes(nbits) bytes of device scratch) gets the tiles' first
 // ranks, one uint64 per tile and the total behind them; totals[0] = entries,
@@ -201,7 +207,6 @@ hipError_t launch_finish_text(uint32_t flags, uint64_t g_start, uint64_t nbits, 
 // launch_primes_emit: the emit launch over tiles [tile0, tile0 + tiles) of a
 // scanned tile_sums: the entry of rank r is stored to out[r - first] exactly
 // when first <= r < first + out_cap and one of those tiles holds it.
-constexpr uint32_t kPrimesTileBits = 256 * 64;
 uint64_t primes_scratch_bytes(uint64_t nbits);
 hipError_t launch_primes_scan(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first,
                               uint64_t out_cap, unsigned long long* totals, void* tile_sums, hipStream_t stream);
@@ -210,12 +215,11 @@ hipError_t launch_primes_emit(uint64_t g_start, uint64_t nbits, const uint64_t* 
                               hipStream_t stream);
 
 // Statistics of a mask (dse_stats.hip): the main launch over `grid` workgroups,
-// each walking its own run of tiles of kStatsTileBits candidates, and the
+// each walking its own run of tiles of kMaskTileBits candidates, and the
 // closing launch, which writes the dse_stats (kStatsWords uint64 words) at
 // `stats`. grid = stats_grid(nbits, CUs of the device, cap or 0): 0 exactly for
 // an empty range, at most kStatsMaxGrid. slabs: stats_scratch_bytes(grid) bytes
 // of device scratch. patterns: npatterns <= 8 host values, passed by value.
-constexpr uint32_t kStatsTileBits = 256 * 64;
 constexpr uint32_t kStatsMaxGrid = 1024;
 constexpr uint32_t kStatsWords = 27 + 1024;
 uint32_t stats_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);

@@ -4,7 +4,7 @@
 //
 // Three launches on the caller's stream, the count / scan / write shape of the
 // base-prime compaction (dse_base.hip) and of the device finish (dse_finish.hip):
-//   primes_size_kernel  per tile of kPrTileWords mask words: its entries (set bits);
+//   primes_size_kernel  per tile of kMaskTileWords mask words: its entries (set bits);
 //   primes_scan_kernel  one workgroup: 64-bit exclusive scan of the tile counts in
 //                       place (the total behind them), and the call's totals;
 //   primes_emit_kernel  per tile: its entries whose rank lies in the call's rank
@@ -18,96 +18,46 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dse_block.h"
 #include "dse_internal.h"
 #include "dse_primes_word.h"
 
 namespace dse {
 namespace {
 
-constexpr uint32_t kPrThreads = 256;
+constexpr uint32_t kPrThreads = kMaskTileWords;  // one mask word per thread
 constexpr uint32_t kPrWaves = kPrThreads / 64;
-constexpr uint32_t kPrTileWords = kPrThreads;  // one mask word per thread
-static_assert(kPrTileWords * 64 == kPrimesTileBits, "dse_internal.h names the tile's candidates");
 // LDS staging window, in entries (16 KiB). A tile of a prime mask near 1e9 holds
 // about 1,600 entries; an all-ones tile holds 16,384 and takes 8 windows.
 constexpr uint32_t kPrWindow = 2048;
 
 struct PrArgs {
-  const uint64_t* mask;
-  uint64_t g_start, nbits, words;
+  MaskRange r;
   uint64_t first, end;  // the rank window [first, end)
 };
 
-// word w of the range as its entries: bits past nbits dropped
-__device__ __forceinline__ uint64_t pr_load_word(const PrArgs& a, uint64_t w) {
-  if (w >= a.words) return 0ull;
-  uint64_t b = a.mask[w];
-  if (w == a.words - 1 && (a.nbits & 63)) b &= (1ull << (a.nbits & 63)) - 1;
-  return b;
-}
-
-// inclusive scan of one count per thread over the workgroup, and its total:
-// shuffles inside a wave, the four wave sums through LDS (one barrier)
-__device__ __forceinline__ uint32_t pr_block_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t x = v;
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[wave] = x;
-  __syncthreads();
-  uint32_t base = 0, sum = 0;
-  for (uint32_t i = 0; i < kPrWaves; ++i) {
-    const uint32_t t = s_wave[i];
-    if (i < wave) base += t;
-    sum += t;
-  }
-  *total = sum;
-  return x + base;
-}
-
 __global__ __launch_bounds__(kPrThreads) void primes_size_kernel(PrArgs a, unsigned long long* __restrict__ sums) {
   __shared__ uint32_t s_wave[kPrWaves];
-  const uint64_t w = (uint64_t)blockIdx.x * kPrTileWords + threadIdx.x;
-  uint32_t c = (uint32_t)__popcll(pr_load_word(a, w));
-  for (uint32_t o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (uint32_t i = 0; i < kPrWaves; ++i) t += s_wave[i];
-    sums[blockIdx.x] = t;
-  }
+  const uint64_t w = (uint64_t)blockIdx.x * kMaskTileWords + threadIdx.x;
+  const uint32_t t = block_sum<kPrThreads>((uint32_t)__popcll(mask_word(a.r, w)), s_wave);
+  if (threadIdx.x == 0) sums[blockIdx.x] = t;
 }
 
 // exclusive scan of the ntiles counts in place, sums[ntiles] = their total;
 // totals[0] = entries of the range, totals[1] = entries inside the rank window
-__global__ __launch_bounds__(1024) void primes_scan_kernel(unsigned long long* __restrict__ sums, uint32_t ntiles,
+__global__ __launch_bounds__(kSliceThreads) void primes_scan_kernel(unsigned long long* __restrict__ sums, uint32_t ntiles,
                                                            uint64_t first, uint64_t out_cap,
                                                            unsigned long long* __restrict__ totals) {
-  __shared__ uint64_t s_c[1024];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t per = (ntiles + 1023) / 1024;
-  const uint32_t b0 = min(ntiles, tid * per), b1 = min(ntiles, b0 + per);
-  uint64_t c = 0;
-  for (uint32_t b = b0; b < b1; ++b) c += sums[b];
-  s_c[tid] = c;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024; o <<= 1) {
-    const uint64_t x = tid >= o ? s_c[tid - o] : 0ull;
-    __syncthreads();
-    s_c[tid] += x;
-    __syncthreads();
-  }
-  uint64_t r = s_c[tid] - c;
-  for (uint32_t b = b0; b < b1; ++b) {
+  __shared__ uint64_t s_wave[kSliceThreads / 64];
+  const ScanSlice<uint64_t> s = slice_scan(ntiles, s_wave, [&](uint32_t b) { return sums[b]; });
+  uint64_t r = s.start;
+  for (uint32_t b = s.b0; b < s.b1; ++b) {
     const uint64_t v = sums[b];
     sums[b] = r;
     r += v;
   }
-  if (tid == 1023) {
-    const uint64_t C = s_c[1023];
+  if (threadIdx.x == 0) {
+    const uint64_t C = s.total;
     sums[ntiles] = C;
     totals[0] = C;
     totals[1] = C > first ? min(out_cap, C - first) : 0ull;
@@ -125,12 +75,12 @@ __global__ __launch_bounds__(kPrThreads) void primes_emit_kernel(PrArgs a, const
   const uint64_t lo = max(r0, a.first), hi = min(r1, a.end);
   if (lo >= hi) return;
 
-  const uint64_t w = t * kPrTileWords + tid;
-  uint64_t bits = pr_load_word(a, w);
+  const uint64_t w = t * kMaskTileWords + tid;
+  uint64_t bits = mask_word(a.r, w);
   const uint32_t c = (uint32_t)__popcll(bits);
   uint32_t tile;
-  uint64_t rank = r0 + (pr_block_scan(c, s_wave, &tile) - c);  // of this word's lowest set bit
-  const uint64_t gw = a.g_start + w * 64ull;
+  uint64_t rank = r0 + (block_scan<kPrThreads>(c, s_wave, &tile) - c);  // of this word's lowest set bit
+  const uint64_t gw = a.r.g_start + w * 64ull;
 
   for (uint64_t b = lo; b < hi; b += kPrWindow) {
     const uint64_t e = min(b + (uint64_t)kPrWindow, hi);
@@ -145,35 +95,23 @@ __global__ __launch_bounds__(kPrThreads) void primes_emit_kernel(PrArgs a, const
   }
 }
 
-inline uint64_t pr_ntiles(uint64_t nbits) {
-  const uint64_t words = (nbits + 63) / 64;
-  return (words + kPrTileWords - 1) / kPrTileWords;
-}
-
 PrArgs pr_args(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first, uint64_t out_cap) {
-  PrArgs a;
-  a.mask = mask;
-  a.g_start = g_start;
-  a.nbits = nbits;
-  a.words = (nbits + 63) / 64;
-  a.first = first;
-  a.end = primes_window_end(first, out_cap);
-  return a;
+  return PrArgs{mask_range(mask, g_start, nbits), first, primes_window_end(first, out_cap)};
 }
 
 }  // namespace
 
-uint64_t primes_scratch_bytes(uint64_t nbits) { return (pr_ntiles(nbits) + 1) * sizeof(unsigned long long); }
+uint64_t primes_scratch_bytes(uint64_t nbits) { return (mask_tiles(nbits) + 1) * sizeof(unsigned long long); }
 
 hipError_t launch_primes_scan(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first,
                               uint64_t out_cap, unsigned long long* totals, void* tile_sums, hipStream_t stream) {
-  const uint64_t ntiles = pr_ntiles(nbits);
+  const uint64_t ntiles = mask_tiles(nbits);
   if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
   unsigned long long* sums = reinterpret_cast<unsigned long long*>(tile_sums);
   if (ntiles)
     hipLaunchKernelGGL(primes_size_kernel, dim3((uint32_t)ntiles), dim3(kPrThreads), 0, stream,
                        pr_args(g_start, nbits, mask, first, out_cap), sums);
-  hipLaunchKernelGGL(primes_scan_kernel, dim3(1), dim3(1024), 0, stream, sums, (uint32_t)ntiles, first, out_cap,
+  hipLaunchKernelGGL(primes_scan_kernel, dim3(1), dim3(kSliceThreads), 0, stream, sums, (uint32_t)ntiles, first, out_cap,
                      totals);
   return hipGetLastError();
 }
@@ -181,7 +119,7 @@ hipError_t launch_primes_scan(uint64_t g_start, uint64_t nbits, const uint64_t* 
 hipError_t launch_primes_emit(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first, uint64_t* out,
                               uint64_t out_cap, const void* tile_sums, uint64_t tile0, uint64_t tiles,
                               hipStream_t stream) {
-  const uint64_t ntiles = pr_ntiles(nbits);
+  const uint64_t ntiles = mask_tiles(nbits);
   if (tile0 > ntiles || tiles > ntiles - tile0 || ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
   if (!tiles || !out_cap) return hipSuccess;
   hipLaunchKernelGGL(primes_emit_kernel, dim3((uint32_t)tiles), dim3(kPrThreads), 0, stream,

@@ -13,20 +13,9 @@ using namespace dse;
 
 namespace {
 
-// what every entry point refuses of a range
-int32_t primes_check_range(uint64_t g_start, uint64_t nbits) {
-  if (int32_t rc = check_odd_range(g_start, nbits)) return rc;
-  if (nbits > (1ull << 44)) return fail(DSE_ERANGE, "primes range above 2^44 candidates in one call");
-  return DSE_OK;
-}
-
 // The tile-sum scratch of the device, ordered against whatever stream used it last.
 int32_t primes_acquire(DevState& d, uint64_t nbits, hipStream_t stream) {
-  StreamScratch& sums = d.primes_sums;
-  // a grow takes half as much again, 64 KiB at least
-  const uint64_t need = primes_scratch_bytes(nbits);
-  HIP_TRY(acquire_scratch(&sums, sums.buf.bytes >= need ? need : std::max<uint64_t>(need + need / 2, 1ull << 16),
-                          stream));
+  HIP_TRY(acquire_scratch_roomy(&d.primes_sums, primes_scratch_bytes(nbits), stream));
   return DSE_OK;
 }
 
@@ -43,9 +32,9 @@ int32_t primes_pipeline(dse_ctx* ctx, DevState& d, uint64_t g_start, uint64_t nb
   if (!nbits) return DSE_OK;
   int32_t rc;
   const uint64_t want = out_cap > (1ull << 40) ? ~0ull : out_cap * 8;
-  if ((rc = ensure_finish_bufs(d, want))) return rc;
-  FinishState& f = d.fin;
-  const uint64_t ntiles = (nbits + kPrimesTileBits - 1) / kPrimesTileBits;
+  if ((rc = ensure_slab_pipe(d, want))) return rc;
+  SlabPipe& f = d.pipe;
+  const uint64_t ntiles = mask_tiles(nbits);
   std::vector<unsigned long long> hsums;
   bool acquired = false;
 
@@ -67,12 +56,11 @@ int32_t primes_pipeline(dse_ctx* ctx, DevState& d, uint64_t g_start, uint64_t nb
 
     uint64_t slab = f.buf_bytes / 8;
     if (ctx->primes_slab_entries) slab = std::min(slab, ctx->primes_slab_entries);
-    bool copy_pending[2] = {false, false};
     int prev_slot = -1;
     uint64_t prev_off = 0, prev_n = 0;
     auto take = [&](int slot, uint64_t off, uint64_t n) -> int32_t {  // once the slab's copy has run
-      HIP_TRY(hipEventSynchronize(f.copy_ev[slot]));
-      std::memcpy(out + off, f.htext[slot].ptr, n * 8);
+      if (int32_t r2 = slab_wait(f, slot)) return r2;
+      std::memcpy(out + off, f.hbuf[slot].ptr, n * 8);
       return DSE_OK;
     };
     int slot = 0;
@@ -81,15 +69,10 @@ int32_t primes_pipeline(dse_ctx* ctx, DevState& d, uint64_t g_start, uint64_t nb
       // tiles [t0, t1): the last tile that starts at or below rank ra, up to the first that starts at or above rb
       const uint64_t t0 = (uint64_t)(std::upper_bound(hsums.begin(), hsums.begin() + ntiles, ra) - hsums.begin()) - 1;
       const uint64_t t1 = (uint64_t)(std::lower_bound(hsums.begin(), hsums.begin() + ntiles, rb) - hsums.begin());
-      uint64_t* const dv = f.dtext[slot].as<uint64_t>();
-      // the slot's device buffer is free once the copy of the slab that used it has run
-      if (copy_pending[slot]) HIP_TRY(hipStreamWaitEvent(d.stream, f.copy_ev[slot], 0));
-      HIP_TRY(launch_primes_emit(g_start, nbits, mask_dev, ra, dv, n, sums, t0, t1 - t0, d.stream));
-      HIP_TRY(hipEventRecord(f.fmt_ev[slot], d.stream));
-      HIP_TRY(hipStreamWaitEvent(f.copy, f.fmt_ev[slot], 0));
-      HIP_TRY(hipMemcpyAsync(f.htext[slot].ptr, dv, n * 8, hipMemcpyDeviceToHost, f.copy));
-      HIP_TRY(hipEventRecord(f.copy_ev[slot], f.copy));
-      copy_pending[slot] = true;
+      if ((r = slab_reuse(f, slot, d.stream))) return r;
+      HIP_TRY(launch_primes_emit(g_start, nbits, mask_dev, ra, f.dbuf[slot].as<uint64_t>(), n, sums, t0, t1 - t0,
+                                 d.stream));
+      if ((r = slab_send(f, slot, n * 8, d.stream))) return r;
       if (prev_slot >= 0 && (r = take(prev_slot, prev_off, prev_n))) return r;
       prev_slot = slot;
       prev_off = off;
@@ -104,10 +87,7 @@ int32_t primes_pipeline(dse_ctx* ctx, DevState& d, uint64_t g_start, uint64_t nb
     const hipError_t e = release_scratch(&d.primes_sums, d.stream);
     if (e != hipSuccess && !rc) rc = fail(DSE_EHIP, std::string("release_scratch failed: ") + hipGetErrorString(e));
   }
-  if (rc) {  // leave nothing in flight on the buffers
-    (void)hipStreamSynchronize(d.stream);
-    if (f.copy) (void)hipStreamSynchronize(f.copy);
-  }
+  if (rc) slab_drain(f, d.stream);
   return rc;
 }
 
@@ -126,7 +106,7 @@ extern "C" int32_t dse_primes_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t
   int32_t rc = primes_check_out(out_dev, out_cap);
   if (rc) return rc;
   if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
-  if ((rc = primes_check_range(g_start, nbits))) return rc;
+  if ((rc = check_mask_range("primes", g_start, nbits))) return rc;
   DevState& d = ctx->devs[0];
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t s = (hipStream_t)stream;
@@ -135,8 +115,7 @@ extern "C" int32_t dse_primes_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t
   hipError_t e = launch_primes_scan(g_start, nbits, mask_dev, first, out_cap,
                                     reinterpret_cast<unsigned long long*>(totals_dev), sums, s);
   if (e == hipSuccess)
-    e = launch_primes_emit(g_start, nbits, mask_dev, first, out_dev, out_cap, sums, 0,
-                           (nbits + kPrimesTileBits - 1) / kPrimesTileBits, s);
+    e = launch_primes_emit(g_start, nbits, mask_dev, first, out_dev, out_cap, sums, 0, mask_tiles(nbits), s);
   HIP_TRY(release_scratch(&d.primes_sums, s));  // also after a failure: what was launched may read the scratch
   if (e != hipSuccess) return fail(DSE_EHIP, std::string("primes launch failed: ") + hipGetErrorString(e));
   return DSE_OK;
@@ -147,7 +126,7 @@ extern "C" int32_t dse_primes_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbi
   if (!ctx) return fail(DSE_EINVAL, "null ctx");
   int32_t rc = primes_check_out(out, out_cap);
   if (rc) return rc;
-  if ((rc = primes_check_range(g_start, nbits))) return rc;
+  if ((rc = check_mask_range("primes", g_start, nbits))) return rc;
   DevState& d = ctx->devs[0];
   if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
   return primes_pipeline(ctx, d, g_start, nbits, d.scratch_mask.as<uint64_t>(), first, out, out_cap, total, written);
@@ -163,7 +142,7 @@ extern "C" int32_t dse_primes_resident(dse_ctx* ctx, int32_t my_num, uint64_t fi
   if ((rc = find_resident(ctx, my_num, &d, &mask))) return rc;
   const uint64_t cs = (uint64_t)ctx->resident.cs;
   const uint64_t g_start = (uint64_t)(my_num - 1) * cs;
-  if ((rc = primes_check_range(g_start, cs))) return rc;
+  if ((rc = check_mask_range("primes", g_start, cs))) return rc;
   HIP_TRY(hipSetDevice(d->device));
   return primes_pipeline(ctx, *d, g_start, cs, mask, first, out, out_cap, total, written);
 }

@@ -5,7 +5,7 @@
 // Two launches on the caller's stream; the launches are the only ordering and
 // no workgroup waits on another:
 //   stats_main_kernel   every workgroup walks its own contiguous run of tiles
-//                       (kStatsTileBits candidates, one mask word per thread;
+//                       (kMaskTileBits candidates, one mask word per thread;
 //                       the words of the next three tiles are already in flight).
 //                       A thread holds its word and the low half of the word
 //                       after it (a plain global load, also across tile and
@@ -29,17 +29,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dse_block.h"
 #include "dse_internal.h"
 #include "dse_stats_word.h"
 
 namespace dse {
 namespace {
 
-constexpr uint32_t kStThreads = 256;
+constexpr uint32_t kStThreads = kMaskTileWords;  // one mask word per thread
 constexpr uint32_t kStWaves = kStThreads / 64;
-constexpr uint32_t kStTileWords = kStThreads;  // one mask word per thread
-constexpr uint32_t kStDepth = 3;               // tiles loaded together, one group ahead of the one worked on
-static_assert(kStTileWords * 64 == kStatsTileBits, "dse_internal.h names the tile's candidates");
+constexpr uint32_t kStDepth = 3;  // tiles loaded together, one group ahead of the one worked on
 // per-thread counters are 32 bits wide and grow by at most 64 per tile: summed into LDS this often
 constexpr uint32_t kStFlushTiles = 1u << 20;
 
@@ -57,30 +56,18 @@ constexpr uint32_t kOutGStart = 0, kOutNbits = 1, kOutPrimes = 2, kOutFirst = 3,
 static_assert(kOutGaps + kStatsBins == kStatsWords, "dse_stats is kStatsWords words");
 
 struct StArgs {
-  const uint64_t* mask;
-  uint64_t g_start, nbits, words;
+  MaskRange r;
   uint64_t ntiles, tiles_per_wg;
   uint64_t last_mask;  // the bits of the last word that lie inside the range
   uint32_t npat;
   uint32_t pat[8];
 };
 
-// word wi of the range from v = mask[min(wi, words - 1)]: stats_load_word's result without a branch
+// Word wi of the range from v = mask[min(wi, words - 1)]: mask_word's result without a branch.
+// The main kernel's tuned variant of the shared load: its raw loads are issued tiles ahead of
+// their use, and the clipping works on what they brought with a precomputed last_mask.
 __device__ __forceinline__ uint64_t st_fix(const StArgs& a, uint64_t wi, uint64_t v) {
-  return wi < a.words ? v & (wi == a.words - 1 ? a.last_mask : ~0ull) : 0ull;
-}
-__device__ __forceinline__ uint64_t st_load(const StArgs& a, uint64_t wi) {  // words >= 1
-  return st_fix(a, wi, a.mask[min(wi, a.words - 1)]);
-}
-
-__device__ __forceinline__ uint32_t st_wave_sum(uint32_t v) {
-  for (uint32_t o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ uint64_t st_wave_sum64(uint64_t v) {
-  for (uint32_t o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-  return v;
+  return wi < a.r.words ? v & (wi == a.r.words - 1 ? a.last_mask : ~0ull) : 0ull;
 }
 
 // the wave's best (longest, then lowest) maximal-gap candidate, in every lane
@@ -147,17 +134,17 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
   auto flush = [&]() {
 #pragma unroll
     for (uint32_t d = 0; d < kStatsSmall; ++d) {
-      const uint32_t r = st_wave_sum(sm[d]);
+      const uint32_t r = wave_sum(sm[d]);
       if (lane == 0 && r) atomicAdd(&s_hist[d + 1], (unsigned long long)r);
       sm[d] = 0;
     }
 #pragma unroll
     for (uint32_t p = 0; p < 8; ++p) {
-      const uint32_t r = st_wave_sum(mt[p]);
+      const uint32_t r = wave_sum(mt[p]);
       if (lane == 0 && r) atomicAdd(&s_acc[p], (unsigned long long)r);
       mt[p] = 0;
     }
-    const uint32_t r = st_wave_sum(pc);
+    const uint32_t r = wave_sum(pc);
     if (lane == 0 && r) atomicAdd(&s_acc[8], (unsigned long long)r);
     pc = 0;
   };
@@ -168,17 +155,17 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
   // after it, as they lie in memory: plain loads at clamped addresses with no use behind them, so
   // all of them stay in flight; tile() drops what lies outside the range (st_fix).
   auto load_group = [&](uint64_t t, uint64_t(&W)[kStDepth], uint32_t(&X)[kStDepth]) {
-    const uint64_t lastw = a.words - 1;
+    const uint64_t lastw = a.r.words - 1;
 #pragma unroll
     for (uint32_t j = 0; j < kStDepth; ++j) {
-      const uint64_t wi = min(t + j, t1 - 1) * kStTileWords + tid;
-      W[j] = a.mask[min(wi, lastw)];
-      X[j] = reinterpret_cast<const uint32_t*>(a.mask)[2 * min(wi + 1, lastw)];
+      const uint64_t wi = min(t + j, t1 - 1) * kMaskTileWords + tid;
+      W[j] = a.r.mask[min(wi, lastw)];
+      X[j] = reinterpret_cast<const uint32_t*>(a.r.mask)[2 * min(wi + 1, lastw)];
     }
   };
   uint32_t since = 0;
   auto tile = [&](uint64_t t, uint64_t wraw, uint32_t xraw) {
-    const uint64_t wi = t * kStTileWords + tid;
+    const uint64_t wi = t * kMaskTileWords + tid;
     const uint64_t pos0 = wi * 64ull;
     const uint64_t w = st_fix(a, wi, wraw);
     const uint32_t nx = (uint32_t)st_fix(a, wi + 1, xraw);
@@ -190,11 +177,7 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
     const uint64_t rem = stats_small_gaps(w, nx, sm);
 
     // exclusive scan (maximum) of "tile position + 1 of the last prime so far"
-    uint32_t x = w ? tid * 64u + stats_msb64(w) + 1u : 0u;
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(x, o);
-      if (lane >= o) x = max(x, y);
-    }
+    const uint32_t x = wave_scan(w ? tid * 64u + stats_msb64(w) + 1u : 0u, ScanMax());
     uint32_t ex = __shfl_up(x, 1);
     if (lane == 0) ex = 0;
     // the waves' maxima through LDS: two sets by tile parity, so one barrier per tile orders them
@@ -207,7 +190,7 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
       if (i < wave) ex = max(ex, u);
       tot = max(tot, u);
     }
-    const uint64_t tile0 = t * (uint64_t)kStatsTileBits;
+    const uint64_t tile0 = t * (uint64_t)kMaskTileBits;
     const uint64_t prev1 = ex ? tile0 + ex : carry;
     if (w) {
       const uint64_t f = pos0 + stats_ctz64(w);
@@ -249,8 +232,8 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
     // ranges): its maximal gap is a short one, found by a second walk
     bi = kStatsNone;
     for (uint64_t t = t0; t < t1; ++t) {
-      const uint64_t wi = t * kStTileWords + tid;
-      stats_small_best(st_load(a, wi), (uint32_t)st_load(a, wi + 1), wi * 64ull, bd, bi);
+      const uint64_t wi = t * kMaskTileWords + tid;
+      stats_small_best(mask_word(a.r, wi), (uint32_t)mask_word(a.r, wi + 1), wi * 64ull, bd, bi);
     }
     st_block_best<kStWaves>(bd, bi, s_bd, s_bi);
   }
@@ -333,7 +316,7 @@ __global__ __launch_bounds__(kClThreads) void stats_close_kernel(StArgs a, const
 #pragma unroll
   for (uint32_t k = 0; k < 10; ++k) {
     const uint32_t src = k < 8 ? kSlMatches + k : k == 8 ? kSlPrimes : kSlOverflow;
-    const uint64_t r = st_wave_sum64(have ? my[src] : 0ull);
+    const uint64_t r = wave_sum(have ? my[src] : 0ull);
     if (lane == 0 && r) atomicAdd(&s_acc[k], (unsigned long long)r);
   }
   if (first != kStatsNone) atomicMin(&s_acc[10], (unsigned long long)first);
@@ -343,36 +326,31 @@ __global__ __launch_bounds__(kClThreads) void stats_close_kernel(StArgs a, const
   }
   st_block_best<kClThreads / 64>(bd, bi, s_bd, s_bi);  // its barriers also order the sums above
   if (tid == 0) {
-    out[kOutGStart] = a.g_start;
-    out[kOutNbits] = a.nbits;
+    out[kOutGStart] = a.r.g_start;
+    out[kOutNbits] = a.r.nbits;
     out[kOutPrimes] = s_acc[8];
-    out[kOutFirst] = s_acc[10] == kStatsNone ? kStatsNone : a.g_start + s_acc[10];
-    out[kOutLast] = last1 ? a.g_start + (last1 - 1) : kStatsNone;
-    const uint64_t head = stats_bits64(a.mask, a.words, a.nbits, 0);
+    out[kOutFirst] = s_acc[10] == kStatsNone ? kStatsNone : a.r.g_start + s_acc[10];
+    out[kOutLast] = last1 ? a.r.g_start + (last1 - 1) : kStatsNone;
+    const uint64_t head = stats_bits64(a.r, 0);
     out[kOutHead] = head;
-    out[kOutTail] = a.nbits >= 64  ? stats_bits64(a.mask, a.words, a.nbits, a.nbits - 64)
-                    : a.nbits == 0 ? 0ull
-                                   : head << (64 - a.nbits);
+    out[kOutTail] = a.r.nbits >= 64  ? stats_bits64(a.r, a.r.nbits - 64)
+                    : a.r.nbits == 0 ? 0ull
+                                     : head << (64 - a.r.nbits);
     out[kOutNPat] = a.npat;
     for (uint32_t p = 0; p < 8; ++p) {
       out[kOutPat + p] = p < a.npat ? a.pat[p] : 0u;
       out[kOutMatches + p] = s_acc[p];
     }
     out[kOutMaxGap] = 2ull * bd;
-    out[kOutMaxGapG] = bd ? a.g_start + bi : kStatsNone;
+    out[kOutMaxGapG] = bd ? a.r.g_start + bi : kStatsNone;
     out[kOutOverflow] = s_acc[9] + s_bins[kClBins];
   }
-}
-
-inline uint64_t st_ntiles(uint64_t nbits) {
-  const uint64_t words = (nbits + 63) / 64;
-  return (words + kStTileWords - 1) / kStTileWords;
 }
 
 }  // namespace
 
 uint32_t stats_grid(uint64_t nbits, int num_cus, uint32_t grid_cap) {
-  const uint64_t ntiles = st_ntiles(nbits);
+  const uint64_t ntiles = mask_tiles(nbits);
   // every workgroup walks one fixed run of tiles, so the grid is one resident round: the main
   // kernel's registers admit 3 workgroups per compute unit (make resources), a fourth would queue
   uint64_t cap = grid_cap ? grid_cap : 3ull * (uint64_t)(num_cus > 0 ? num_cus : 1);
@@ -388,12 +366,9 @@ hipError_t launch_stats(uint64_t g_start, uint64_t nbits, const uint64_t* mask, 
                         uint32_t npatterns, uint64_t* stats, void* slabs, uint32_t grid, hipStream_t stream) {
   if (npatterns > 8 || grid > kStatsMaxGrid) return hipErrorInvalidValue;
   StArgs a;
-  a.mask = mask;
-  a.g_start = g_start;
-  a.nbits = nbits;
-  a.words = (nbits + 63) / 64;
+  a.r = mask_range(mask, g_start, nbits);
   a.last_mask = (nbits & 63) ? (1ull << (nbits & 63)) - 1 : ~0ull;
-  a.ntiles = st_ntiles(nbits);
+  a.ntiles = mask_tiles(nbits);
   if ((a.ntiles != 0) != (grid != 0)) return hipErrorInvalidValue;
   a.tiles_per_wg = grid ? (a.ntiles + grid - 1) / grid : 0;
   a.npat = npatterns;

@@ -4,7 +4,6 @@
 // (dse_stats_range, dse_stats_resident); dse_stats_merge joins the results of
 // adjacent ranges by host arithmetic, and dse_debug_stats_host runs the
 // kernels' per-word bodies (dse_stats_word.h) on the host.
-#include <algorithm>
 #include <cstring>
 
 #include "dse_host.h"
@@ -17,12 +16,6 @@ static_assert(DSE_STATS_WORDS == kStatsWords && DSE_STATS_GAP_BINS == kStatsBins
               "the kernels write the struct of include/dse.h");
 
 namespace {
-
-int32_t stats_check_range(uint64_t g_start, uint64_t nbits) {
-  if (int32_t rc = check_odd_range(g_start, nbits)) return rc;
-  if (nbits > (1ull << 44)) return fail(DSE_ERANGE, "stats range above 2^44 candidates in one call");
-  return DSE_OK;
-}
 
 int32_t stats_check_patterns(const uint32_t* patterns, uint32_t npatterns) {
   if (npatterns > DSE_STATS_MAX_PATTERNS) return fail(DSE_EINVAL, "more than 8 patterns");
@@ -38,7 +31,7 @@ int32_t stats_acquire(DevState& d, uint32_t grid, uint32_t nres, hipStream_t str
   StreamScratch& s = d.stats_scratch;
   const uint64_t slabs = stats_scratch_bytes(grid);
   const uint64_t need = slabs + (uint64_t)nres * sizeof(dse_stats);
-  HIP_TRY(acquire_scratch(&s, s.buf.bytes >= need ? need : std::max<uint64_t>(need + need / 2, 1ull << 16), stream));
+  HIP_TRY(acquire_scratch_roomy(&s, need, stream));
   if (res) *res = reinterpret_cast<uint64_t*>(static_cast<char*>(s.buf.ptr) + slabs);
   return DSE_OK;
 }
@@ -87,7 +80,7 @@ extern "C" int32_t dse_stats_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t 
   if (reinterpret_cast<uintptr_t>(stats_dev) & 7u) return fail(DSE_EINVAL, "stats_dev is not 8-byte aligned");
   int32_t rc;
   if ((rc = stats_check_patterns(patterns, npatterns))) return rc;
-  if ((rc = stats_check_range(g_start, nbits))) return rc;
+  if ((rc = check_mask_range("stats", g_start, nbits))) return rc;
   DevState& d = ctx->devs[0];
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t s = (hipStream_t)stream;
@@ -105,7 +98,7 @@ extern "C" int32_t dse_stats_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbit
   if (!ctx || !out) return fail(DSE_EINVAL, "null ctx or out");
   int32_t rc;
   if ((rc = stats_check_patterns(patterns, npatterns))) return rc;
-  if ((rc = stats_check_range(g_start, nbits))) return rc;
+  if ((rc = check_mask_range("stats", g_start, nbits))) return rc;
   DevState& d = ctx->devs[0];
   if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
   HIP_TRY(hipSetDevice(d.device));
@@ -128,7 +121,7 @@ extern "C" int32_t dse_stats_resident(dse_ctx* ctx, int32_t my_num, const uint32
     return fail(DSE_EINVAL, "chunk " + std::to_string(my_num) + " is not resident");
   const uint64_t cs = (uint64_t)r.cs;
   const int32_t k0 = my_num ? my_num : 1, k1 = my_num ? my_num : r.P;
-  if ((rc = stats_check_range((uint64_t)(k1 - 1) * cs, cs))) return rc;
+  if ((rc = check_mask_range("stats", (uint64_t)(k1 - 1) * cs, cs))) return rc;
 
   // every device's chunks are enqueued on its stream before any result is waited for
   const size_t nd = ctx->devs.size();
@@ -240,8 +233,8 @@ extern "C" int32_t dse_debug_stats_host(const uint64_t* mask, uint64_t g_start, 
   if (nbits && !mask) return fail(DSE_EINVAL, "null mask");
   int32_t rc;
   if ((rc = stats_check_patterns(patterns, npatterns))) return rc;
-  if ((rc = stats_check_range(g_start, nbits))) return rc;
-  const uint64_t words = (nbits + 63) / 64;
+  if ((rc = check_mask_range("stats", g_start, nbits))) return rc;
+  const MaskRange m = mask_range(mask, g_start, nbits);
   dse_stats r;
   std::memset(&r, 0, sizeof r);
   r.g_start = g_start;
@@ -261,9 +254,9 @@ extern "C" int32_t dse_debug_stats_host(const uint64_t* mask, uint64_t g_start, 
     }
   };
   // the main kernel's tile loop, one word at a time: the scan's result is the loop's carry
-  for (uint64_t wi = 0; wi < words; ++wi) {
-    const uint64_t w = stats_load_word(mask, words, nbits, wi);
-    const uint32_t nx = (uint32_t)stats_load_word(mask, words, nbits, wi + 1);
+  for (uint64_t wi = 0; wi < m.words; ++wi) {
+    const uint64_t w = mask_word(m, wi);
+    const uint32_t nx = (uint32_t)mask_word(m, wi + 1);
     const uint64_t pos0 = wi * 64;
     r.primes += stats_pop64(w);
     for (uint32_t p = 0; p < npatterns; ++p) r.matches[p] += stats_pattern_word(w, nx, patterns[p]);
@@ -279,13 +272,12 @@ extern "C" int32_t dse_debug_stats_host(const uint64_t* mask, uint64_t g_start, 
     }
   }
   if (bd == 0 && carry != 0)
-    for (uint64_t wi = 0; wi < words; ++wi)
-      stats_small_best(stats_load_word(mask, words, nbits, wi), (uint32_t)stats_load_word(mask, words, nbits, wi + 1),
-                       wi * 64, bd, bi);
+    for (uint64_t wi = 0; wi < m.words; ++wi)
+      stats_small_best(mask_word(m, wi), (uint32_t)mask_word(m, wi + 1), wi * 64, bd, bi);
   // the closing kernel's scalar members
   if (carry) r.last_g = g_start + (carry - 1);
-  r.head = stats_bits64(mask, words, nbits, 0);
-  r.tail = nbits >= 64 ? stats_bits64(mask, words, nbits, nbits - 64) : nbits == 0 ? 0ull : r.head << (64 - nbits);
+  r.head = stats_bits64(m, 0);
+  r.tail = nbits >= 64 ? stats_bits64(m, nbits - 64) : nbits == 0 ? 0ull : r.head << (64 - nbits);
   r.max_gap = 2 * bd;
   if (bd) r.max_gap_g = g_start + bi;
   *out = r;

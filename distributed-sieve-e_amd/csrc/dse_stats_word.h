@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dse_mask.h"
+
 namespace dse {
 
 constexpr uint32_t kStatsSmall = 16;    // gaps of up to this many places are counted bit-parallel
@@ -35,22 +37,12 @@ __host__ __device__ __forceinline__ uint32_t stats_ctz64(uint64_t x) { return (u
 __host__ __device__ __forceinline__ uint32_t stats_msb64(uint64_t x) { return 63u - (uint32_t)__builtin_clzll(x); }
 __host__ __device__ __forceinline__ uint32_t stats_pop64(uint64_t x) { return (uint32_t)__builtin_popcountll(x); }
 
-// word wi of the range: bits past nbits dropped, 0 past the last word
-__host__ __device__ __forceinline__ uint64_t stats_load_word(const uint64_t* mask, uint64_t words, uint64_t nbits,
-                                                             uint64_t wi) {
-  if (wi >= words) return 0ull;
-  uint64_t b = mask[wi];
-  if (wi == words - 1 && (nbits & 63)) b &= (1ull << (nbits & 63)) - 1;
-  return b;
-}
-
 // positions [s, s + 64) of the range as one word (bit k = position s + k; 0 past nbits)
-__host__ __device__ __forceinline__ uint64_t stats_bits64(const uint64_t* mask, uint64_t words, uint64_t nbits,
-                                                          uint64_t s) {
+__host__ __device__ __forceinline__ uint64_t stats_bits64(const MaskRange& r, uint64_t s) {
   const uint64_t wi = s >> 6;
   const uint32_t sh = (uint32_t)(s & 63);
-  uint64_t v = stats_load_word(mask, words, nbits, wi) >> sh;
-  if (sh) v |= stats_load_word(mask, words, nbits, wi + 1) << (64 - sh);
+  uint64_t v = mask_word(r, wi) >> sh;
+  if (sh) v |= mask_word(r, wi + 1) << (64 - sh);
   return v;
 }
 

@@ -24,8 +24,8 @@ ERRORS = {
     -7: "DSE_EINTERNAL",
 }
 
-# Candidates per tile of the dse_primes_* kernels (csrc/dse_internal.h
-# kPrimesTileBits; dse_debug_get_stat "primes_tile_bits" reports the library's).
+# Candidates per tile of the dse_primes_* kernels (csrc/dse_mask.h
+# kMaskTileBits; dse_debug_get_stat "primes_tile_bits" reports the library's).
 PRIMES_TILE_BITS = 256 * 64
 
 # include/dse.h dse_stats as uint64 words, and where its members start

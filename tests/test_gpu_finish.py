@@ -174,6 +174,23 @@ def test_hack_on_a_large_range(torch, ctx, tmp_path):
         assert cnt == n and got == want, dbl
 
 
+@pytest.mark.parametrize("r", [0, 7])
+def test_more_tiles_than_scan_threads(torch, ctx, tmp_path, r):
+    """1,025 tiles of 16,384 candidates and 37 more: the single-workgroup scan over the tiles'
+    (entries, bytes) pairs has 1,024 threads, so here a thread owns two tiles, one or none. A
+    mask of about one bit in 1,000, first_rank 0 and 7, byte for byte against the host writer
+    (first_rank r as in test_first_rank_0_to_9: r entries printed in front, then cut off)."""
+    g, nbits = 10**9, 1025 * 16384 + 37
+    bits = np.random.default_rng(17).random(nbits) < 1 / 1000
+    bits[0] = bits[-1] = True
+    full = host_file(tmp_path, 2, g - r, nbits + r, pack(np.concatenate([np.ones(r, bool), bits])))
+    prefix = host_file(tmp_path, 2, g - r, r, pack(np.ones(r, bool))) if r else b""
+    skip = len(prefix) - 1 if r else 0  # the prefix's entries without its closing "\n"
+    assert full[:skip] == prefix[:skip]
+    got, cnt = device_text(torch, ctx, LAST, g, nbits, pack(bits), first_rank=r)
+    assert cnt == int(bits.sum()) and got == full[skip:]
+
+
 # -- 3. rank carry -----------------------------------------------------------------
 def test_rank_carries_across_a_split(torch, ctx, tmp_path):
     """Every word holds 11 entries, so a first part of k words holds 11k = k (mod 10)."""

@@ -79,11 +79,19 @@ def test_tile_constant_is_the_librarys(ctx):
 
 
 # -- 1. arbitrary masks ----------------------------------------------------------
-NBITS = [1, 63, 64, 65, T - 1, T, T + 1, 2 * T + 37, 2**20 + 37]
+# MANY tiles and more: the single-workgroup scan over the tile counts has 1,024 threads. At 1,024
+# tiles every thread owns exactly one count; at 1,025 a thread owns two (or the last one, or none:
+# the slices' ends are clamped), the smallest range at which a scan thread loops.
+MANY = 1024 * T
+NBITS = [1, 63, 64, 65, T - 1, T, T + 1, 2 * T + 37, 2**20 + 37, MANY, MANY + T + 37]
 
 
 def patterns(nbits, seed):
     rng = np.random.default_rng(seed)
+    if nbits >= MANY:  # about one bit in 1,000, so the values stay a few hundred KB; both ends set
+        bits = rng.random(nbits) < 1 / 1000
+        bits[0] = bits[-1] = True
+        return {"thousandth": bits}
     out = {"half": rng.random(nbits) < 0.5, "twentieth": rng.random(nbits) < 1 / 20,
            "zero": np.zeros(nbits, bool), "ones": np.ones(nbits, bool)}
     for name, pos in (("first", 0), ("last", nbits - 1), ("seam-", T - 1), ("seam+", T)):

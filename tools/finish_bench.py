@@ -19,13 +19,10 @@ import argparse
 import hashlib
 import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "distributed-sieve-e_amd"))
+from bench_common import events, ms, timed  # also: the package path, DSE_LIB
 
 HBM_TBS = 8.0
 SLAB_BYTES = 64 << 20
@@ -49,16 +46,6 @@ def sha256_file(path: str) -> str:
         for blk in iter(lambda: f.read(1 << 24), b""):
             h.update(blk)
     return h.hexdigest()
-
-
-def timed(fn, reps):
-    fn()  # warm-up
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return statistics.median(ts), ts
 
 
 def main() -> int:
@@ -99,8 +86,8 @@ def main() -> int:
         size = os.path.getsize(pa)
         ha, hb = sha256_file(pa), sha256_file(pb)
         print(f"sieve_all alone                       median {s_med * 1e3:10.2f} ms")
-        print(f"(a) sieve_all + copy mask + host writer median {a_med * 1e3:10.2f} ms   all {[round(t * 1e3, 1) for t in a_all]}")
-        print(f"(b) sieve_all + finish_resident         median {b_med * 1e3:10.2f} ms   all {[round(t * 1e3, 1) for t in b_all]}")
+        print(f"(a) sieve_all + copy mask + host writer median {a_med * 1e3:10.2f} ms   all {ms(a_all)}")
+        print(f"(b) sieve_all + finish_resident         median {b_med * 1e3:10.2f} ms   all {ms(b_all)}")
         print(f"file: {size} bytes; sha256 (a) {ha}")
         print(f"                    sha256 (b) {hb}   equal: {ha == hb}")
 
@@ -126,30 +113,17 @@ def main() -> int:
         text = torch.empty(SLAB_BYTES, dtype=torch.uint8, device="cuda")
         pinned = torch.empty(SLAB_BYTES, dtype=torch.uint8).pin_memory()
 
-        def events(fn):
-            fn()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(args.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1) * 1e-3)
-            return statistics.median(ts), ts
-
         c_med, c_all = events(lambda: ctx.finish_text_dev_async(flags, 0, nbits, mask.data_ptr(), 0, text.data_ptr(),
-                                                                SLAB_BYTES, tot.data_ptr(), sp))
-        d_med, d_all = events(lambda: pinned[:text_bytes].copy_(text[:text_bytes], non_blocking=True))
+                                                                SLAB_BYTES, tot.data_ptr(), sp), args.reps)
+        d_med, d_all = events(lambda: pinned[:text_bytes].copy_(text[:text_bytes], non_blocking=True), args.reps)
         assert int(tot[1]) == text_bytes
         want = open(pa, "rb").read(text_bytes)
         slab_ok = pinned[:text_bytes].numpy().tobytes() == want
         gbs = text_bytes / c_med / 1e9
         print(f"slab: {words} mask words, {int(tot[0])} entries, {text_bytes} text bytes; equals the file's head: {slab_ok}")
-        print(f"(c) size + scan + emit launches  median {c_med * 1e3:8.3f} ms   all {[round(t * 1e3, 3) for t in c_all]}"
+        print(f"(c) size + scan + emit launches  median {c_med * 1e3:8.3f} ms   all {ms(c_all, 3)}"
               f"   {gbs:.1f} GB/s of text ({gbs / (HBM_TBS * 1e3):.4f} of the {HBM_TBS:g} TB/s HBM figure)")
-        print(f"(d) D2H copy of the slab's text  median {d_med * 1e3:8.3f} ms   all {[round(t * 1e3, 3) for t in d_all]}"
+        print(f"(d) D2H copy of the slab's text  median {d_med * 1e3:8.3f} ms   all {ms(d_all, 3)}"
               f"   {text_bytes / d_med / 1e9:.1f} GB/s")
         print(f"(b) < (a): {b_med < a_med}   (c) < (d): {c_med < d_med}")
         print(json.dumps({"N": N, "P": P, "reps": args.reps, "file_bytes": size, "sha256_equal": ha == hb,

@@ -19,47 +19,9 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
-import signal
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "distributed-sieve-e_amd"))
-
-
-class step_limit:
-    """SIGALRM after `seconds`: the process exits 124 at once (no further GPU work)."""
-
-    def __init__(self, name: str, seconds: int):
-        self.name, self.seconds = name, seconds
-
-    def _expired(self, *_):
-        sys.stderr.write(f"primes_bench: step '{self.name}' exceeded {self.seconds} s; stopping\n")
-        sys.stderr.flush()
-        os._exit(124)
-
-    def __enter__(self):
-        signal.signal(signal.SIGALRM, self._expired)
-        signal.alarm(self.seconds)
-
-    def __exit__(self, *exc):
-        signal.alarm(0)
-
-
-def timed(fn, reps):
-    fn()  # warm-up
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return statistics.median(ts), ts
-
-
-def ms(ts, nd=1):
-    return [round(t * 1e3, nd) for t in ts]
+from bench_common import events, ms, step_limit, timed  # also: the package path, DSE_LIB
 
 
 def main() -> int:
@@ -114,28 +76,16 @@ def main() -> int:
         tot = torch.zeros(2, dtype=torch.int64, device="cuda")
         sp = torch.cuda.current_stream().cuda_stream
 
-        def events(fn):
-            fn()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(args.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1) * 1e-3)
-            return statistics.median(ts), ts
-
         with step_limit("(c) launches", lim):
             c_med, c_all = events(lambda: ctx.primes_dev_async(0, nbits, mask.data_ptr(), 0, out.data_ptr(), count,
-                                                               tot.data_ptr(), sp))
+                                                               tot.data_ptr(), sp), args.reps)
             totals = [int(x) for x in tot.cpu()]
             equal_c = bool(np.array_equal(out.cpu().numpy().view(np.uint64), res["b"]))
         with step_limit("(c0) count only", lim):
-            c0_med, c0_all = events(lambda: ctx.primes_dev_async(0, nbits, mask.data_ptr(), 0, 0, 0, tot.data_ptr(), sp))
+            c0_med, c0_all = events(lambda: ctx.primes_dev_async(0, nbits, mask.data_ptr(), 0, 0, 0, tot.data_ptr(), sp),
+                                    args.reps)
         with step_limit("(d) device copy", lim):
-            d_med, d_all = events(lambda: dup.copy_(out, non_blocking=True))
+            d_med, d_all = events(lambda: dup.copy_(out, non_blocking=True), args.reps)
             equal_d = bool(torch.equal(dup, out))
         ratio = c_med / d_med
         print(f"(c) size + scan + emit launches   median {c_med * 1e3:8.3f} ms   all {ms(c_all, 3)}"

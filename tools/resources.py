@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel resource usage (VGPR / SGPR / spills / LDS / occupancy) of every
-kernel of the wheel translation units, one line per kernel, compiled with the
+kernel of every translation unit, one line per kernel, compiled with the
 Makefile's per-TU flags. Used to check that a source change leaves the
 production kernels' register allocation as it was."""
 import os
@@ -23,7 +23,7 @@ def make_var(name):
 def main(extra):
     tus = [("dse_wheel.hip", make_var("WHEEL_FLAGS")), ("dse_bucket.hip", make_var("WHEEL_FLAGS")),
            ("dse_wheel_half.hip", make_var("WHEEL_FLAGS")), ("dse_wheel_plain.hip", make_var("PLAIN_FLAGS")),
-           ("dse_base.hip", [])]
+           ("dse_base.hip", []), ("dse_finish.hip", []), ("dse_primes.hip", []), ("dse_stats.hip", [])]
     for tu, fl in tus:
         if not os.path.exists(os.path.join(CSRC, tu)):
             continue

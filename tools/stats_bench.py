@@ -21,47 +21,9 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
-import signal
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "distributed-sieve-e_amd"))
-
-
-class step_limit:
-    """SIGALRM after `seconds`: the process exits 124 at once (no further GPU work)."""
-
-    def __init__(self, name: str, seconds: int):
-        self.name, self.seconds = name, seconds
-
-    def _expired(self, *_):
-        sys.stderr.write(f"stats_bench: step '{self.name}' exceeded {self.seconds} s; stopping\n")
-        sys.stderr.flush()
-        os._exit(124)
-
-    def __enter__(self):
-        signal.signal(signal.SIGALRM, self._expired)
-        signal.alarm(self.seconds)
-
-    def __exit__(self, *exc):
-        signal.alarm(0)
-
-
-def timed(fn, reps):
-    fn()  # warm-up
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return statistics.median(ts), ts
-
-
-def ms(ts, nd=1):
-    return [round(t * 1e3, nd) for t in ts]
+from bench_common import events, ms, step_limit, timed  # also: the package path, DSE_LIB
 
 
 def host_numbers(np, primes, patterns):
@@ -153,28 +115,17 @@ def main() -> int:
             torch.cuda.synchronize()
             ctx.device_status()
 
-        def events(fn):
-            fn()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(args.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1) * 1e-3)
-            return statistics.median(ts), ts
-
         mb = mask.numel() * 8
         with step_limit("(c) statistics launches", lim):
             c_med, c_all = events(lambda: ctx.stats_dev_async(0, nbits, mask.data_ptr(), S.CONSTELLATIONS,
-                                                              dst.data_ptr(), sp))
+                                                              dst.data_ptr(), sp), args.reps)
             equal_c = bool(np.array_equal(dst.cpu().numpy().view(np.uint64), st.words))
         with step_limit("(c1) statistics launches, no patterns", lim):
-            c1_med, c1_all = events(lambda: ctx.stats_dev_async(0, nbits, mask.data_ptr(), (), dst.data_ptr(), sp))
+            c1_med, c1_all = events(lambda: ctx.stats_dev_async(0, nbits, mask.data_ptr(), (), dst.data_ptr(), sp),
+                                    args.reps)
         with step_limit("(c0) count only", lim):
-            c0_med, c0_all = events(lambda: ctx.primes_dev_async(0, nbits, mask.data_ptr(), 0, 0, 0, tot.data_ptr(), sp))
+            c0_med, c0_all = events(lambda: ctx.primes_dev_async(0, nbits, mask.data_ptr(), 0, 0, 0, tot.data_ptr(), sp),
+                                    args.reps)
             equal_c = equal_c and int(tot[0].item()) == st.primes
         print(f"(c) statistics launches, 7 patterns  median {c_med * 1e3:8.3f} ms   all {ms(c_all, 3)}"
               f"   (mask read: {mb / c_med / 1e9:.1f} GB/s); equals (b): {equal_c}")
@@ -189,7 +140,7 @@ def main() -> int:
             vals = torch.zeros(st.primes, dtype=torch.int64, device="cuda")
             with step_limit("(e) extraction launches", lim):
                 e_med, e_all = events(lambda: ctx.primes_dev_async(0, nbits, mask.data_ptr(), 0, vals.data_ptr(),
-                                                                   st.primes, tot.data_ptr(), sp))
+                                                                   st.primes, tot.data_ptr(), sp), args.reps)
             print(f"(e) extraction launches, {8 * st.primes / 1e6:.1f} MB written median {e_med * 1e3:8.3f} ms"
                   f"   all {ms(e_all, 3)}   (c) <= (e): {c_med <= e_med}")
             out.update(e_extraction_ms=e_med * 1e3)
