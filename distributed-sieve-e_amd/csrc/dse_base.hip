@@ -225,7 +225,8 @@ hipError_t launch_base_primes_big(uint64_t limit, void* table, uint32_t cap, int
   if (e != hipSuccess) return e;
   if ((e = hipMemsetAsync(cnt, 0, sizeof(*cnt), stream)) != hipSuccess) return e;
   // sqrt(limit) < 2^16 <= kWheelMaxPrime: no bucketed pass, no scratch
-  e = launch_sieve_range(t0, 0, nb, reinterpret_cast<uint32_t*>(mask), cnt, num_cus, stream, nullptr, nullptr);
+  e = launch_sieve_range(t0, 0, nb, reinterpret_cast<uint32_t*>(mask), cnt, num_cus, stream, nullptr, nullptr,
+                         nullptr);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(compact_count_kernel, dim3(nblocks), dim3(kCompactThreads), 0, stream, mask, words, sums);
   hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kSliceThreads), 0, stream, sums, nblocks, table, cap, limit);

@@ -706,7 +706,7 @@ hipError_t ensure_scratch(Scratch* sc, uint64_t bytes, hipStream_t stream, char*
 // A range whose primes reach above kWheelMaxPrime: bucketed passes.
 hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,
                            unsigned long long* count, int num_cus, hipStream_t stream, Scratch* scratch,
-                           const SieveOpts* opts) {
+                           const SieveOpts* opts, PlanStats* plan) {
   const uint64_t vmax = 3 + 2 * (g_start + nbits - 1);
   const uint64_t root = isqrt64(vmax);
   uint64_t plane_lut;
@@ -821,6 +821,11 @@ hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, 
     // always the instantiation with bucket units: wa.bk_start points into the scratch, never null
     if ((e = launch_wheel_bucketed(table, wa, num_cus, stream)) != hipSuccess) return fail_pass(e);
     if ((e = release_scratch(scratch, stream)) != hipSuccess) return e;
+    if (plan) {
+      plan->add_wheel_launch(wa.nseg, wheel_grid(wa.nseg, num_cus));
+      ++plan->bucket_passes;
+      plan->bucket_max_pass_segments = std::max(plan->bucket_max_pass_segments, ns);
+    }
     s0 += ns;
   }
   return hipSuccess;

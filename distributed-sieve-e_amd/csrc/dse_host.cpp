@@ -469,6 +469,7 @@ int32_t dse::sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t n
   int32_t rc;
   HIP_TRY(hipSetDevice(d.device));
   const uint64_t words = (nbits + 63) / 64;
+  ctx->plan = PlanStats();
   if ((rc = build_table(d, dse_base_limit_for_range(g0, nbits)))) return rc;
   HIP_TRY(grow_buf(&d.counts, sizeof(unsigned long long)));
   const bool dev_mask = mask_or_null || keep_dev;
@@ -477,7 +478,7 @@ int32_t dse::sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t n
   unsigned long long* counts = d.counts.as<unsigned long long>();
   HIP_TRY(hipMemsetAsync(counts, 0, sizeof(unsigned long long), d.stream));
   HIP_TRY(launch_sieve_range(d.table.ptr, g0, nbits, dev_mask ? d.scratch_mask.as<uint32_t>() : nullptr, counts,
-                             d.num_cus, d.stream, &d.scratch, &ctx->opts));
+                             d.num_cus, d.stream, &d.scratch, &ctx->opts, &ctx->plan));
   unsigned long long c = 0;
   HIP_TRY(hipMemcpyAsync(&c, counts, sizeof(c), hipMemcpyDeviceToHost, d.stream));
   if (mask_or_null && words)
@@ -639,10 +640,11 @@ int32_t dse_sieve_range_dev_async(dse_ctx* ctx, const void* table_dev, uint64_t 
   if (!ctx || !table_dev || !count_dev) return fail(DSE_EINVAL, "null ctx, table or count");
   int32_t rc = check_odd_range(g_start, nbits);
   if (rc) return rc;
+  ctx->plan = PlanStats();
   HIP_TRY(hipSetDevice(ctx->devs[0].device));
   HIP_TRY(launch_sieve_range(table_dev, g_start, nbits, reinterpret_cast<uint32_t*>(mask_dev),
                              reinterpret_cast<unsigned long long*>(count_dev), ctx->devs[0].num_cus,
-                             (hipStream_t)stream, &ctx->devs[0].scratch, &ctx->opts));
+                             (hipStream_t)stream, &ctx->devs[0].scratch, &ctx->opts, &ctx->plan));
   return DSE_OK;
 }
 
@@ -679,6 +681,7 @@ int32_t dse_sieve_all(dse_ctx* ctx, int64_t n, int32_t P, uint64_t* per_chunk_co
   // every chunk and the tail are covered by the primes <= sqrt(largest odd <= n)
   const uint64_t limit = dse_base_limit_for_range(0, (uint64_t)P * (uint64_t)cs + tail_n);
   const uint64_t nc = (uint64_t)P + 1;  // per-chunk counts + tail
+  ctx->plan = PlanStats();
 
   // resident masks: one device buffer per chunk, on its device
   if ((rc = ensure_resident(ctx, n, P, cs))) return rc;
@@ -699,7 +702,8 @@ int32_t dse_sieve_all(dse_ctx* ctx, int64_t n, int32_t P, uint64_t* per_chunk_co
       rs.push_back({(uint64_t)k * (uint64_t)cs, (uint64_t)cs, ctx->resident.masks[k].as<uint32_t>(),
                     counts + k});
     if (i == nd - 1 && tail_n) rs.push_back({tail_g, tail_n, nullptr, counts + P});
-    HIP_TRY(launch_sieve_ranges(d.table.ptr, rs.data(), rs.size(), d.num_cus, d.stream, &d.scratch, &ctx->opts));
+    HIP_TRY(launch_sieve_ranges(d.table.ptr, rs.data(), rs.size(), d.num_cus, d.stream, &d.scratch, &ctx->opts,
+                                &ctx->plan));
   }
 
   // counts: RCCL all-reduce (each slot is non-zero on exactly one device)
@@ -741,6 +745,7 @@ int32_t dse_sieve_window(dse_ctx* ctx, uint64_t lo, uint64_t hi, uint64_t* count
                                 "; the device base-prime build supports " + std::to_string(kBigBaseLimitMax));
   const int nd = (int)ctx->devs.size();
   int32_t rc;
+  ctx->plan = PlanStats();
   if ((rc = prepare_devices(ctx, limit, 1))) return rc;
   // one table, built on device 0 and RCCL-broadcast (as dse_sieve_all)
   if ((rc = share_table(ctx, limit))) return rc;
@@ -752,7 +757,7 @@ int32_t dse_sieve_window(dse_ctx* ctx, uint64_t lo, uint64_t hi, uint64_t* count
     const uint64_t s = std::min<uint64_t>(nb, part * i), e = std::min<uint64_t>(nb, part * (i + 1));
     if (e > s)
       HIP_TRY(launch_sieve_range(d.table.ptr, g0 + s, e - s, nullptr, d.counts.as<unsigned long long>(), d.num_cus,
-                                 d.stream, &d.scratch, &ctx->opts));
+                                 d.stream, &d.scratch, &ctx->opts, &ctx->plan));
   }
   unsigned long long c = 0;
   if ((rc = collect_counts(ctx, 1, &c))) return rc;
@@ -825,6 +830,18 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     int c = 0;
     if (!ctx->comms.empty()) NCCL_TRY(ncclCommCount(ctx->comms[0], &c));
     *value = c;
+  } else if (n == "plan_wheel_launches") {
+    *value = (int64_t)ctx->plan.wheel_launches;
+  } else if (n == "plan_full_segments") {
+    *value = (int64_t)ctx->plan.full_segments;
+  } else if (n == "plan_half_segments") {
+    *value = (int64_t)ctx->plan.half_segments;
+  } else if (n == "plan_max_rounds") {
+    *value = (int64_t)ctx->plan.max_rounds;
+  } else if (n == "plan_bucket_passes") {
+    *value = (int64_t)ctx->plan.bucket_passes;
+  } else if (n == "plan_bucket_max_pass_segments") {
+    *value = (int64_t)ctx->plan.bucket_max_pass_segments;
   } else if (n == "primes_tile_bits") {
     *value = (int64_t)kMaskTileBits;
   } else if (n == "stats_tile_bits") {

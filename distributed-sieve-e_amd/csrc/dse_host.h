@@ -101,6 +101,7 @@ struct dse_ctx {
   bool rccl_single = false;
   int64_t rccl_calls = 0;          // collectives RCCL accepted (dse_debug_get_stat)
   int64_t table_local_builds = 0;  // tables built per device instead of broadcast (share_table)
+  dse::PlanStats plan;             // what the last sieving entry point launched (dse_debug_get_stat "plan_*")
   dse::Buf lg_stage;               // gathered counts [devs][n]
   dse::Buf lg_sum;                 // their sum [n]
   hipEvent_t lg_done = nullptr;    // the sum on device 0's stream

@@ -133,6 +133,28 @@ struct SieveOpts {
   uint64_t table_bcast_max = 0;   // > 0: broadcast cap of share_table in bytes (0: DSE_TABLE_BROADCAST_MAX_BYTES)
 };
 
+// Test-only: what launch_sieve_ranges planned, as host-side counters read
+// through dse_debug_get_stat ("plan_*", include/dse.h). The launchers add to
+// the PlanStats they are given (null: nothing is recorded); a sieving entry
+// point clears its context's before its first launch.
+struct PlanStats {
+  uint64_t wheel_launches = 0;          // launches of the wheel kernel, either geometry, with or without bucket units
+  uint64_t full_segments = 0;           // full-size segments launched without bucket units
+  uint64_t half_segments = 0;           // half-size segments launched
+  uint64_t max_rounds = 0;              // largest ceil(segments / workgroups) of a wheel launch
+  uint64_t bucket_passes = 0;           // bucketed passes
+  uint64_t bucket_max_pass_segments = 0;  // segments of the largest one
+  // one wheel launch of `nseg` segments over `grid` workgroups (wheel_grid)
+  void add_wheel_launch(uint32_t nseg, uint32_t grid) {
+    ++wheel_launches;
+    max_rounds = max_rounds > (nseg + grid - 1) / grid ? max_rounds : (nseg + grid - 1) / grid;
+  }
+};
+
+// Workgroups of a persistent launch of the wheel kernel over nseg >= 1
+// segments: one per CU, at most one per segment.
+inline uint32_t wheel_grid(uint32_t nseg, int num_cus) { return nseg < (uint32_t)num_cus ? nseg : (uint32_t)num_cus; }
+
 // out[j] = sum_i in[i * n + j], i < nsrc (dse_debug_init_logical's count all-reduce)
 hipError_t launch_sum_rows(const unsigned long long* in, uint32_t nsrc, uint32_t n, unsigned long long* out,
                            hipStream_t stream);
@@ -154,27 +176,27 @@ struct RangeSpec {
 // share persistent launches of the wheel kernel (several chunks of one
 // device: one launch, no idle partial rounds between them); ranges whose
 // sqrt(max value) exceeds kWheelMaxPrime run their bucketed passes one by one
-// (they need `scratch`). `opts` may be null. Empty ranges are skipped.
+// (they need `scratch`). `opts` and `plan` may be null. Empty ranges are skipped.
 hipError_t launch_sieve_ranges(const void* table, const RangeSpec* rs, size_t n, int num_cus, hipStream_t stream,
-                               Scratch* scratch, const SieveOpts* opts);
+                               Scratch* scratch, const SieveOpts* opts, PlanStats* plan);
 // Sieve odd indices [g_start, g_start+nbits) with the mod-30 wheel kernel: out
 // (may be null) gets the mask as 32-bit words (2*ceil(nbits/64) of them, upper
 // half of the last uint64 zeroed); *count (device) is incremented. Ranges whose
 // sqrt(max value) exceeds kWheelMaxPrime need `scratch` (bucketed pass);
-// `opts` may be null.
+// `opts` and `plan` may be null.
 hipError_t launch_sieve_range(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,
                               unsigned long long* count, int num_cus, hipStream_t stream, Scratch* scratch,
-                              const SieveOpts* opts);
+                              const SieveOpts* opts, PlanStats* plan);
 // A range whose primes reach above kWheelMaxPrime, as bucketed passes
 // (dse_bucket.hip; launch_sieve_ranges routes such ranges here).
 hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,
                            unsigned long long* count, int num_cus, hipStream_t stream, Scratch* scratch,
-                           const SieveOpts* opts);
+                           const SieveOpts* opts, PlanStats* plan);
 // The same sieve with the half-size segment geometry (2^16 periods,
 // dse_wheel_half.hip): launch_sieve_ranges gives it the segments past the last
 // full round of a launch when that finishes sooner. No bucketed primes.
 hipError_t launch_wheel_ranges_half(const void* table, const RangeSpec* rs, size_t n, int num_cus,
-                                    hipStream_t stream);
+                                    hipStream_t stream, PlanStats* plan);
 // One persistent launch of the full-geometry wheel kernel over wa (built by
 // make_wheel_args, dse_wheel_geometry.h, in a unit of the full geometry), one
 // per instantiation, each in a unit with its own compile flags: without bucket

@@ -115,7 +115,7 @@ constexpr double kHalfSegCost = DSE_HALF_SEG_COST, kLaunchCost = DSE_LAUNCH_COST
 // go to the half-size geometry instead when that finishes sooner: (their
 // half segments / num_cus rounds) x kHalfSegCost plus the second launch.
 hipError_t launch_pooled(const void* table, const RangeSpec* rs, size_t n, int num_cus, hipStream_t stream,
-                         const SieveOpts* opts) {
+                         const SieveOpts* opts, PlanStats* plan) {
   if (n == 0) return hipSuccess;
   const uint32_t geo = opts ? opts->wheel_geometry : 0;  // 0 auto, 1 full only, 2 half only
   constexpr uint64_t kHalfBits = kWheelOutBits / 2;
@@ -144,15 +144,17 @@ hipError_t launch_pooled(const void* table, const RangeSpec* rs, size_t n, int n
       full.assign(rs, rs + n);
     }
   }
-  hipError_t e = launch_wheel_batches(launch_wheel_plain, table, full.data(), full.size(), num_cus, stream);
+  hipError_t e = launch_wheel_batches(launch_wheel_plain, table, full.data(), full.size(), num_cus, stream, plan,
+                                      &PlanStats::full_segments);
   if (e != hipSuccess) return e;
-  return half.empty() ? hipSuccess : launch_wheel_ranges_half(table, half.data(), half.size(), num_cus, stream);
+  return half.empty() ? hipSuccess
+                      : launch_wheel_ranges_half(table, half.data(), half.size(), num_cus, stream, plan);
 }
 
 }  // namespace
 
 hipError_t launch_sieve_ranges(const void* table, const RangeSpec* rs, size_t n, int num_cus, hipStream_t stream,
-                               Scratch* scratch, const SieveOpts* opts) {
+                               Scratch* scratch, const SieveOpts* opts, PlanStats* plan) {
   // ranges of up to 2^30 segments (the launch's 32-bit segment indices)
   constexpr uint64_t kMaxBits = (1ull << 30) * kWheelOutBits;
   std::vector<RangeSpec> pooled;
@@ -164,19 +166,19 @@ hipError_t launch_sieve_ranges(const void* table, const RangeSpec* rs, size_t n,
         pooled.push_back(piece);
       } else {
         const hipError_t e = launch_bucketed(table, piece.g_start, piece.nbits, piece.out, piece.count, num_cus,
-                                             stream, scratch, opts);
+                                             stream, scratch, opts, plan);
         if (e != hipSuccess) return e;
       }
     }
   }
-  return launch_pooled(table, pooled.data(), pooled.size(), num_cus, stream, opts);
+  return launch_pooled(table, pooled.data(), pooled.size(), num_cus, stream, opts, plan);
 }
 
 hipError_t launch_sieve_range(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,
                               unsigned long long* count, int num_cus, hipStream_t stream, Scratch* scratch,
-                              const SieveOpts* opts) {
+                              const SieveOpts* opts, PlanStats* plan) {
   const RangeSpec rs{g_start, nbits, out, count};
-  return launch_sieve_ranges(table, &rs, 1, num_cus, stream, scratch, opts);
+  return launch_sieve_ranges(table, &rs, 1, num_cus, stream, scratch, opts, plan);
 }
 
 }  // namespace dse

@@ -96,15 +96,20 @@ WheelArgs make_wheel_args(const RangeSpec* rs, uint32_t n, uint64_t* plane_lut,
 // Launches over rs[0..n), kMaxRanges ranges at a time, built for this unit's
 // geometry (make_wheel_args): launch(table, wa, num_cus, stream) must launch
 // a kernel of the same one (launch_wheel_plain from dse_wheel.hip,
-// launch_wheel<false> in dse_wheel_half.hip).
+// launch_wheel<false> in dse_wheel_half.hip). plan (may be null) counts the
+// launches, and their segments in plan->*segs.
 template <typename Launch>
 hipError_t launch_wheel_batches(Launch launch, const void* table, const RangeSpec* rs, size_t n, int num_cus,
-                                hipStream_t stream) {
+                                hipStream_t stream, PlanStats* plan, uint64_t PlanStats::*segs) {
   for (size_t i = 0; i < n; i += kMaxRanges) {
     uint64_t plane_lut;
-    const hipError_t e = launch(
-        table, make_wheel_args(rs + i, (uint32_t)std::min<size_t>(kMaxRanges, n - i), &plane_lut), num_cus, stream);
+    const WheelArgs wa = make_wheel_args(rs + i, (uint32_t)std::min<size_t>(kMaxRanges, n - i), &plane_lut);
+    const hipError_t e = launch(table, wa, num_cus, stream);
     if (e != hipSuccess) return e;
+    if (plan && wa.nseg) {
+      plan->add_wheel_launch(wa.nseg, wheel_grid(wa.nseg, num_cus));
+      plan->*segs += wa.nseg;
+    }
   }
   return hipSuccess;
 }

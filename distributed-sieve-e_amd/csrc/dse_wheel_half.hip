@@ -13,8 +13,8 @@ namespace dse {
 // The tail of a launch whose last round of full segments would leave most
 // CUs idle (launch_pooled, dse_wheel.hip). Primes <= kWheelMaxPrime only.
 hipError_t launch_wheel_ranges_half(const void* table, const RangeSpec* rs, size_t n, int num_cus,
-                                    hipStream_t stream) {
-  return launch_wheel_batches(launch_wheel<false>, table, rs, n, num_cus, stream);
+                                    hipStream_t stream, PlanStats* plan) {
+  return launch_wheel_batches(launch_wheel<false>, table, rs, n, num_cus, stream, plan, &PlanStats::half_segments);
 }
 
 }  // namespace dse

@@ -1308,7 +1308,7 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
 template <bool BK>
 hipError_t launch_wheel(const void* table, const WheelArgs& wa, int num_cus, hipStream_t stream) {
   if (wa.nseg == 0) return hipSuccess;
-  const uint32_t grid = std::min<uint32_t>(wa.nseg, (uint32_t)num_cus);
+  const uint32_t grid = wheel_grid(wa.nseg, num_cus);
   hipLaunchKernelGGL(wheel_segments_kernel<BK>, dim3(grid), dim3(NT), 0, stream, table, wa);
   return hipGetLastError();
 }

@@ -396,6 +396,25 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   of broadcast (one per device and call);
  *   "primes_tile_bits": candidates per tile of the dse_primes_* kernels;
  *   "stats_tile_bits": candidates per tile of the dse_stats_* kernels.
+ * The "plan_*" names describe what the context's most recent sieving entry
+ * point (dse_sieve_odd_range, dse_sieve_chunk, dse_sieve_all, dse_sieve_window,
+ * dse_sieve_range_dev_async, and the calls that sieve a range before they
+ * finish, extract or count it) launched to sieve its ranges: host-side
+ * counters, cleared when the entry point begins, summed over the context's
+ * devices (the two maxima: taken over them). The launches that build a base
+ * table are not counted. A test that is about later rounds, the full / half
+ * split or several super-buckets asserts them, so that it fails when its
+ * shape stops producing what it is about (another CU count, other cost
+ * constants):
+ *   "plan_wheel_launches": launches of the wheel kernel (the batches of 9
+ *   ranges of a pooled launch and the bucketed passes count one each);
+ *   "plan_full_segments": full-size segments launched without bucket units;
+ *   "plan_half_segments": half-size segments launched;
+ *   "plan_max_rounds": the largest ceil(segments / workgroups) of a wheel
+ *   launch, workgroups = min(segments, CUs): above 1, workgroups carried
+ *   state from one segment to their next;
+ *   "plan_bucket_passes": bucketed passes;
+ *   "plan_bucket_max_pass_segments": the largest of them, in segments.
  * DSE_EINVAL for an unknown name. */
 int32_t dse_debug_get_stat(dse_ctx *ctx, const char *name, int64_t *value);
 

@@ -201,6 +201,36 @@ def top(g: dict) -> None:
     g["top"] = res
 
 
+ROUNDS_NB = 260 * TOP_SEG_BITS + 777         # tests/test_gpu_rounds.py (i): 261 segments, ragged start and end
+ROUNDS_G0 = {"1e16": 10**16 // 2 + 12345, "1e18": (10**18 + 1 - 3) // 2 + 12345}
+
+
+def rounds(g: dict) -> None:
+    """Bucketed ranges of more segments than a device has CUs, at 1e16 and 1e18
+    (the production band 1, p > 2^28): count, mask SHA-256 and the prime count
+    of every segment of 1,966,080 candidates from g0 on. Before an entry is
+    written, 4,096 seeded random candidates of its range are checked against
+    deterministic Miller-Rabin (tests/primes_ref.py)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from primes_ref import is_prime_mr, mask_bits
+    res = {}
+    for name, g0 in ROUNDS_G0.items():
+        t = time.time()
+        m, c = o.fast_sieve_range(g0, ROUNDS_NB)
+        bits = mask_bits(m, ROUNDS_NB)
+        rng = np.random.default_rng(0x5EED)
+        for j in rng.integers(0, ROUNDS_NB, 4096):
+            assert bool(bits[j]) == is_prime_mr(3 + 2 * (g0 + int(j))), (name, 3 + 2 * (g0 + int(j)))
+        seg = np.add.reduceat(bits.astype(np.int64), np.arange(0, ROUNDS_NB, TOP_SEG_BITS))
+        assert int(seg.sum()) == int(c) == int(bits.sum())
+        res[name] = {"g0": g0, "nb": ROUNDS_NB, "count": int(c), "mask_sha256": sha(m),
+                     "segment_counts": [int(x) for x in seg],
+                     "source": "fast_sieve_range, 4,096 seeded random candidates checked against Miller-Rabin "
+                               "(tests/primes_ref.py) when generated"}
+        print(f"rounds {name}: {int(c)} primes ({time.time() - t:.1f}s)", flush=True)
+    g["rounds"] = res
+
+
 def main():
     """Default: regenerate the small fixtures (sweep, files, 1e9). Flags add or
     refresh sections of the existing golden.json in place:
@@ -209,9 +239,10 @@ def main():
       --big11    1e11 P=1/2/4/8 (streamed)
       --big12    1e12 P=8 (streamed, ~10 min on 8 cores)
       --window   the [1e18, 1e18+1e10] count
-      --top      base-table primes to 1e9 and 2^31 - 1, and the last segments below 2^62"""
+      --top      base-table primes to 1e9 and 2^31 - 1, and the last segments below 2^62
+      --rounds   261 bucketed segments at 1e16 and at 1e18 (about 3 min of oracle time)"""
     flags = set(sys.argv[1:])
-    incremental = flags & {"--ref1e10", "--big11", "--big12", "--window", "--top"}
+    incremental = flags & {"--ref1e10", "--big11", "--big12", "--window", "--top", "--rounds"}
     if incremental and os.path.exists(OUT):
         g = json.load(open(OUT))
     else:
@@ -227,6 +258,8 @@ def main():
         window(g)
     if "--top" in flags:
         top(g)
+    if "--rounds" in flags:
+        rounds(g)
     with open(OUT, "w") as f:
         json.dump(g, f, indent=1)
     print("wrote", OUT)

@@ -210,3 +210,20 @@ def test_golden_top_entries():
     s = top["segments"]
     assert s["nb"] == 5 * 1_966_080 + 777 and 3 + 2 * (s["g0"] + s["nb"] - 1) == 2**62 - 1
     assert all("source" in e for e in top.values())
+
+
+def test_golden_rounds_entries():
+    """GOLDEN["rounds"] (make_golden.py --rounds, tests/test_gpu_rounds.py):
+    260 segments + 777 candidates from a ragged start at 1e16 and at 1e18, the
+    261 per-segment prime counts summing to the count, within 1% of the
+    density 2 / ln v of primes among odd numbers."""
+    import math
+    r = GOLDEN["rounds"]
+    assert set(r) == {"1e16", "1e18"}
+    assert r["1e16"]["g0"] == 10**16 // 2 + 12345 and r["1e18"]["g0"] == (10**18 + 1 - 3) // 2 + 12345
+    for e in r.values():
+        assert e["nb"] == 260 * 1_966_080 + 777 and e["g0"] % 15 and e["g0"] % 64
+        assert len(e["segment_counts"]) == 261 and sum(e["segment_counts"]) == e["count"]
+        assert all(0 < c < 1_966_080 for c in e["segment_counts"][:-1]) and 0 <= e["segment_counts"][-1] <= 777
+        assert abs(e["count"] / (e["nb"] * 2 / math.log(2 * e["g0"])) - 1) < 0.01
+        assert len(e["mask_sha256"]) == 64 and "Miller-Rabin" in e["source"]
