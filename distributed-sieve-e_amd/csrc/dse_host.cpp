@@ -3,7 +3,7 @@
 // points, debug options and stats, and what the other host units share (range
 // checks, scratch growth, the two-slot slab pipe). The finish side is
 // dse_finish_host.cpp, primes as numbers dse_primes_host.cpp, statistics
-// dse_stats_host.cpp.
+// dse_stats_host.cpp, rank and select dse_query_host.cpp.
 //
 // Replaces the reference's orchestration of the hot path:
 //   spread-work (sieve.clj:15-34)            -> dse_spread_work (exact int64)
@@ -269,8 +269,11 @@ int32_t free_resident(dse_ctx* ctx) {
   for (size_t k = 0; k < r.masks.size(); ++k) {
     HIP_TRY(hipSetDevice(ctx->devs[k % ctx->devs.size()].device));
     HIP_TRY(free_buf(&r.masks[k]));
+    if (k < r.index.size()) HIP_TRY(free_buf(&r.index[k]));  // every query call has drained its stream
   }
   r.masks.clear();
+  r.index.clear();
+  r.indexed.clear();
   return DSE_OK;
 }
 
@@ -287,6 +290,11 @@ int32_t ensure_resident(dse_ctx* ctx, int64_t n, int32_t P, int64_t cs) {
   r.cs = cs;
   r.words = ((uint64_t)cs + 63) / 64;
   r.masks.assign((size_t)P, Buf());
+  r.index.assign((size_t)P, Buf());
+  r.indexed.assign((size_t)P, 0);
+  r.total.assign((size_t)P, 0);
+  r.first.assign((size_t)P, DSE_QUERY_NONE);
+  r.last.assign((size_t)P, DSE_QUERY_NONE);
   for (int32_t k = 0; k < P; ++k) {
     hipError_t e = hipSetDevice(ctx->devs[(size_t)k % ctx->devs.size()].device);
     if (e == hipSuccess) e = grow_buf(&r.masks[k], r.words * 8);
@@ -460,6 +468,7 @@ const struct {
     {"primes_slab_entries", 0, kI64Max, "must be >= 0",
      [](dse_ctx* c, int64_t v) { c->primes_slab_entries = (uint64_t)v; }},
     {"stats_grid", 0, (int64_t)kStatsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->stats_grid = (uint32_t)v; }},
+    {"query_grid", 0, (int64_t)kQueryMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->query_grid = (uint32_t)v; }},
 };
 
 }  // namespace
@@ -570,6 +579,7 @@ void dse_destroy(dse_ctx* ctx) {
     (void)free_scratch(&d.finish_sums);
     (void)free_scratch(&d.primes_sums);
     (void)free_scratch(&d.stats_scratch);
+    (void)free_scratch(&d.query_scratch);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }
@@ -846,6 +856,8 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     *value = (int64_t)kMaskTileBits;
   } else if (n == "stats_tile_bits") {
     *value = (int64_t)kMaskTileBits;
+  } else if (n == "query_index_builds") {
+    *value = ctx->query_index_builds;
   } else {
     return fail(DSE_EINVAL, "unknown stat " + n);
   }

@@ -1,8 +1,8 @@
 // dse_host.h -- shared by the units of the C-ABI host layer (dse_host.cpp:
 // contexts, tables, collectives, sieve entry points; dse_finish_host.cpp: the
 // primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
-// dse_stats_host.cpp: statistics of a mask). Not installed; include/dse.h is
-// the ABI.
+// dse_stats_host.cpp: statistics of a mask; dse_query_host.cpp: rank and
+// select). Not installed; include/dse.h is the ABI.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -66,6 +66,7 @@ struct DevState {
   StreamScratch finish_sums; // device finish (dse_finish.hip): tile-sum scratch of the three launches
   StreamScratch primes_sums; // primes as numbers (dse_primes.hip): tile-sum scratch of the three launches
   StreamScratch stats_scratch; // statistics (dse_stats.hip): the workgroups' slabs, and results on their way to the host
+  StreamScratch query_scratch; // rank and select (dse_query.hip): queries and answers on their way, dse_query_range's index
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
 };
 
@@ -80,6 +81,14 @@ struct ResidentSet {
   int64_t cs = 0;                // candidates per chunk
   uint64_t words = 0;            // uint64 words per mask
   std::vector<Buf> masks;        // [P], of `words` uint64 each
+  // Rank and select (dse_query_host.cpp): chunk k's rank index, built on its device at the first
+  // query that needs it and freed with the masks. Behind the index's words and the scan's two
+  // totals the buffer holds the two queries and two answers that fetched `first` and `last`.
+  std::vector<Buf> index;        // [P]
+  std::vector<char> indexed;     // [P]: index, total, first and last are this mask's
+  std::vector<uint64_t> total;   // [P]: entries of the chunk
+  std::vector<uint64_t> first;   // [P]: value of its first entry, DSE_QUERY_NONE for an empty chunk
+  std::vector<uint64_t> last;    // [P]: of its last
 };
 
 }  // namespace dse
@@ -92,6 +101,8 @@ struct dse_ctx {
   uint64_t finish_slab_words = 0;  // test-only: > 0 caps a finish slab at that many mask words
   uint64_t primes_slab_entries = 0;  // test-only: > 0 caps a slab of dse_primes_range / _resident at that many values
   uint32_t stats_grid = 0;  // test-only: > 0 caps the workgroups of a statistics launch
+  uint32_t query_grid = 0;  // test-only: > 0 caps the workgroups of a query launch
+  int64_t query_index_builds = 0;  // rank indices built for resident chunks (dse_debug_get_stat)
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:
   bool logical = false;

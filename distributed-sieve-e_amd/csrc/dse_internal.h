@@ -1,9 +1,9 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
-// dse_primes.hip, dse_stats.hip) and the C-ABI host layer (dse_host.cpp,
-// dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp). Not installed;
+// dse_primes.hip, dse_stats.hip, dse_query.hip) and the C-ABI host layer (dse_host.cpp,
+// dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp, dse_query_host.cpp). Not installed;
 // include/dse.h is the ABI. The units that read a resident mask (finish,
-// primes, stats) share its range, tiles and clipped word load (dse_mask.h);
+// primes, stats, query) share its range, tiles and clipped word load (dse_mask.h);
 // every unit with a workgroup sum or scan takes it from dse_block.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -248,5 +248,20 @@ uint32_t stats_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
 uint64_t stats_scratch_bytes(uint32_t grid);
 hipError_t launch_stats(uint64_t g_start, uint64_t nbits, const uint64_t* mask, const uint32_t* patterns,
                         uint32_t npatterns, uint64_t* stats, void* slabs, uint32_t grid, hipStream_t stream);
+
+// Rank and select on a mask (dse_query.hip). The index of a range is the scanned
+// tile sums of launch_primes_scan (first = 0, out_cap = 0): query_index_words(nbits)
+// uint64 words, index[t] = entries in the tiles before t, index[tiles] = the total;
+// the scan's two totals are written behind them. launch_query: out[i] = the answer
+// to q[i] for kind = kQuery* (dse_query_word.h; the DSE_QUERY_* of include/dse.h),
+// over `grid` workgroups = query_grid(kind, nq, CUs of the device, cap or 0): at
+// most kQueryGridPerCu per CU, so a wave (a lane for kQueryTest) takes several
+// queries of a large batch. kQueryTest reads no index.
+constexpr uint32_t kQueryGridPerCu = 8;
+constexpr uint32_t kQueryMaxGrid = 1024;  // of the test-only cap
+uint64_t query_index_words(uint64_t nbits);
+uint32_t query_grid(uint32_t kind, uint64_t nq, int num_cus, uint32_t grid_cap);
+hipError_t launch_query(uint32_t kind, uint64_t g_start, uint64_t nbits, const uint64_t* mask, const void* index,
+                        const uint64_t* q, uint64_t nq, uint64_t* out, uint32_t grid, hipStream_t stream);
 
 }  // namespace dse

@@ -31,6 +31,10 @@ PRIMES_TILE_BITS = 256 * 64
 # include/dse.h dse_stats as uint64 words, and where its members start
 STATS_WORDS, STATS_GAP_BINS, STATS_MAX_PATTERNS, STATS_NONE = 27 + 1024, 1024, 8, (1 << 64) - 1
 
+# include/dse.h DSE_QUERY_*
+QUERY_NONE = (1 << 64) - 1
+QUERY_RANK, QUERY_SELECT, QUERY_NEXT, QUERY_PREV, QUERY_TEST = range(5)
+
 # name -> (restype, argtypes); every symbol include/dse.h declares.
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _vp, _cp = ctypes.c_void_p, ctypes.c_char_p
@@ -74,6 +78,12 @@ SIGNATURES = {
     "dse_stats_range": (_i32, [_vp, _u64, _u64, _pu32, _u32, _pu64]),
     "dse_stats_resident": (_i32, [_vp, _i32, _pu32, _u32, _pu64]),
     "dse_stats_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_query_index_bytes": (_u64, [_u64]),
+    "dse_query_index_dev_async": (_i32, [_vp, _u64, _u64, _vp, _vp, _u64, _vp]),
+    "dse_query_dev_async": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "dse_query_range": (_i32, [_vp, _u32, _u64, _u64, _pu64, _u64, _pu64]),
+    "dse_query_resident": (_i32, [_vp, _i32, _u32, _pu64, _u64, _pu64]),
+    "dse_debug_query_host": (_i32, [_pu64, _u64, _u64, _u32, _pu64, _u64, _pu64]),
     "dse_debug_stats_host": (_i32, [_pu64, _u64, _u64, _pu32, _u32, _pu64]),
     "dse_debug_finish_format": (_i32, [_u64, ctypes.c_uint32, ctypes.c_char_p]),
     "dse_debug_primes_word": (_i32, [_u64, _u64, _u64, _u64, _u64, _pu64]),

@@ -147,6 +147,7 @@ class Context:
             self._ptr = L.dse_init_device(device) if device is not None else L.dse_init(num_gpus)
         if not self._ptr:
             raise _dse.DseError(L.dse_last_status(), "dse_init", L.dse_last_error().decode(errors="replace"))
+        self._run = None  # (n, P, cs, pi_ref) of the last sieve_all: what prime_pi and its kin answer about
 
     @property
     def ptr(self):
@@ -195,8 +196,10 @@ class Context:
         """-> (per-chunk counts, pi_ref, pi_full); masks stay on the devices."""
         counts = np.zeros(P, dtype=np.uint64)
         pr, pf = ctypes.c_uint64(), ctypes.c_uint64()
+        self._run = None
         check(lib().dse_sieve_all(self.ptr, n, P, u64p(counts), ctypes.byref(pr), ctypes.byref(pf)),
               "dse_sieve_all")
+        self._run = (n, P, _spread(n, P)[0], pr.value)
         return counts, pr.value, pf.value
 
     def copy_chunk_mask(self, n: int, P: int, my_num: int) -> np.ndarray:
@@ -346,6 +349,151 @@ class Context:
             return self.stats_range(min((a - 3) // 2, 1 << 62), 0, patterns)
         b = hi if hi & 1 else hi - 1
         return self.stats_range((a - 3) // 2, (b - a) // 2 + 1, patterns)
+
+
+    # -- rank and select ---------------------------------------------------------
+    def query_index_dev_async(self, g_start: int, nbits: int, mask_ptr: int, index_ptr: int, index_bytes: int,
+                              stream_ptr: int = 0):
+        """The rank index of a device mask into query_index_bytes(nbits) bytes of
+        device memory (include/dse.h dse_query_index_dev_async): index[t] = entries
+        in the tiles before t, index[tiles] = the total."""
+        check(lib().dse_query_index_dev_async(self.ptr, g_start, nbits, mask_ptr or None, index_ptr or None,
+                                              index_bytes, stream_ptr or None),
+              "dse_query_index_dev_async")
+
+    def query_dev_async(self, kind: int, g_start: int, nbits: int, mask_ptr: int, index_ptr: int, q_ptr: int,
+                        nq: int, out_ptr: int, stream_ptr: int = 0):
+        """out[i] = the answer of QUERY_* `kind` to q[i], all in device memory
+        (include/dse.h dse_query_dev_async)."""
+        check(lib().dse_query_dev_async(self.ptr, kind, g_start, nbits, mask_ptr or None, index_ptr or None,
+                                        q_ptr or None, nq, out_ptr or None, stream_ptr or None),
+              "dse_query_dev_async")
+
+    def query_range(self, kind: int, g_start: int, nbits: int, q) -> np.ndarray:
+        """gen-table + sieve-e of an odd-index range, its rank index and the
+        answers of `kind` to the queries q, computed on the device."""
+        qa, out = _queries(q)
+        check(lib().dse_query_range(self.ptr, kind, g_start, nbits, u64p(qa) if len(qa) else None, len(qa),
+                                    u64p(out) if len(qa) else None), "dse_query_range")
+        return out
+
+    def resident_query(self, kind: int, q, my_num: Optional[int] = None) -> np.ndarray:
+        """The answers of `kind` to the queries q from a chunk the last sieve_all
+        left on its device, or (my_num=None) from all its chunks as the one
+        range [3, 3 + 2 P cs): only queries and answers cross to the host."""
+        qa, out = _queries(q)
+        check(lib().dse_query_resident(self.ptr, 0 if my_num is None else my_num, kind,
+                                       u64p(qa) if len(qa) else None, len(qa), u64p(out) if len(qa) else None),
+              "dse_query_resident")
+        return out
+
+    # What the run left by sieve_all knows about the primes, the prime 2 counted:
+    # each takes one integer or an array of them and answers in kind. The masks
+    # cover the odd values up to `bound` = 3 + 2 P cs - 2, so every integer up to
+    # bound + 1 (an even number) is known; a question that needs a value above
+    # that raises ValueError and names the first such query.
+    def _covered(self):
+        """-> (last covered value 3 + 2 P cs - 2, pi_ref) of the last sieve_all"""
+        if self._run is None:
+            raise ValueError("no sieve_all run is resident in this context")
+        _, P, cs, pi_ref = self._run
+        return 1 + 2 * P * cs, pi_ref
+
+    @staticmethod
+    def _ints(x, what: str):
+        """-> (Python ints, x was a scalar); every one in 0 .. 2^64 - 1"""
+        scalar = np.ndim(x) == 0
+        vals = [int(v) for v in np.atleast_1d(np.asarray(x, dtype=object)).ravel()]
+        for v in vals:
+            if v < 0 or v >= 1 << 64:
+                raise ValueError(f"{what}({v}): outside 0 .. 2^64 - 1")
+        return vals, scalar
+
+    def _ask(self, kind: int, vals) -> List[int]:
+        return [int(v) for v in self.resident_query(kind, np.array(vals, dtype=np.uint64))]
+
+    def prime_pi(self, x):
+        """The number of primes <= x, from the resident masks."""
+        bound, _ = self._covered()
+        vals, scalar = self._ints(x, "prime_pi")
+        for v in vals:
+            if v > bound + 1:
+                raise ValueError(f"prime_pi({v}): the resident masks cover the values up to {bound}")
+        got = [r + (v >= 2) for r, v in zip(self._ask(QUERY_RANK, vals), vals)]
+        return got[0] if scalar else np.array(got, dtype=np.uint64)
+
+    def nth_prime(self, n):
+        """The n-th prime, 1-based: nth_prime(1) == 2."""
+        bound, pi_ref = self._covered()
+        vals, scalar = self._ints(n, "nth_prime")
+        for v in vals:
+            if v < 1:
+                raise ValueError("nth_prime(0): ranks start at 1")
+            if v > pi_ref:
+                raise ValueError(f"nth_prime({v}): the resident masks hold the first {pi_ref} primes (up to {bound})")
+        got = self._ask(QUERY_SELECT, [max(v, 2) - 2 for v in vals])
+        got = [2 if v == 1 else g for g, v in zip(got, vals)]
+        return got[0] if scalar else np.array(got, dtype=np.uint64)
+
+    def next_prime(self, x):
+        """The smallest prime > x."""
+        bound, _ = self._covered()
+        vals, scalar = self._ints(x, "next_prime")
+        got = [2 if v < 2 else g for g, v in zip(self._ask(QUERY_NEXT, vals), vals)]
+        for g, v in zip(got, vals):
+            if g == QUERY_NONE:
+                raise ValueError(f"next_prime({v}): no prime above it among the covered values up to {bound}")
+        return got[0] if scalar else np.array(got, dtype=np.uint64)
+
+    def prev_prime(self, x):
+        """The largest prime < x; None for x <= 2 (in an array: 0)."""
+        bound, _ = self._covered()
+        vals, scalar = self._ints(x, "prev_prime")
+        for v in vals:
+            if v > bound + 2:  # bound + 1 is even: every value below bound + 2 is covered
+                raise ValueError(f"prev_prime({v}): the resident masks cover the values up to {bound}")
+        got = [(None if v <= 2 else 2) if g == QUERY_NONE else g for g, v in zip(self._ask(QUERY_PREV, vals), vals)]
+        return got[0] if scalar else np.array([g or 0 for g in got], dtype=np.uint64)
+
+    def is_prime(self, x):
+        """Whether x is prime."""
+        bound, _ = self._covered()
+        vals, scalar = self._ints(x, "is_prime")
+        for v in vals:
+            if v > bound + 1:
+                raise ValueError(f"is_prime({v}): the resident masks cover the values up to {bound}")
+        got = [bool(t) or v == 2 for t, v in zip(self._ask(QUERY_TEST, vals), vals)]
+        return got[0] if scalar else np.array(got, dtype=bool)
+
+
+# include/dse.h DSE_QUERY_*
+QUERY_NONE = _dse.QUERY_NONE
+QUERY_RANK, QUERY_SELECT, QUERY_NEXT, QUERY_PREV, QUERY_TEST = (_dse.QUERY_RANK, _dse.QUERY_SELECT, _dse.QUERY_NEXT,
+                                                                _dse.QUERY_PREV, _dse.QUERY_TEST)
+
+
+def _queries(q):
+    """-> (the queries as a contiguous uint64 array, an answer array of the same length)"""
+    if not (isinstance(q, np.ndarray) and q.dtype == np.uint64):
+        q = np.asarray(q, dtype=object).astype(np.uint64)  # Python integers up to 2^64 - 1, exactly
+    qa = np.ascontiguousarray(np.atleast_1d(q)).ravel()
+    return qa, np.empty(len(qa), dtype=np.uint64)
+
+
+def query_index_bytes(nbits: int) -> int:
+    """Bytes of the rank index of a range of nbits candidates."""
+    return int(lib().dse_query_index_bytes(nbits))
+
+
+def query_host(mask: np.ndarray, g_start: int, nbits: int, kind: int, q) -> np.ndarray:
+    """Test-only: the query kernel's per-word and per-tile bodies run on the host
+    over a host mask (include/dse.h dse_debug_query_host)."""
+    qa, out = _queries(q)
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    check(lib().dse_debug_query_host(u64p(m) if len(m) else None, g_start, nbits, kind,
+                                     u64p(qa) if len(qa) else None, len(qa), u64p(out) if len(qa) else None),
+          "dse_debug_query_host")
+    return out
 
 
 def base_table_bytes(limit: int) -> int:

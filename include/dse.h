@@ -344,6 +344,64 @@ int32_t dse_stats_resident(dse_ctx *ctx, int32_t my_num,
  * or empty). */
 int32_t dse_stats_merge(const dse_stats *a, const dse_stats *b, dse_stats *out);
 
+/* ---- rank and select ------------------------------------------------------ */
+
+/* Questions about single values or ranks, answered on the GPU from a device-resident mask and its
+ * rank index; a query reads one tile of the mask (2 KiB) and only the answers cross to the host.
+ * All semantics are over the mask's entries: an entry is a set bit, its value 3 + 2(g_start + bit
+ * index); the entries are ranked 0, 1, 2, ... in increasing order, the ranks of dse_primes_*. The
+ * prime 2 is in no mask. Every x in 0 .. UINT64_MAX is legal for every kind: even, below 3, below
+ * or above the range. */
+#define DSE_QUERY_NONE   UINT64_MAX
+#define DSE_QUERY_RANK   0u  /* in: value x  -> entries with value <= x (0 below the range, the total at or above its end) */
+#define DSE_QUERY_SELECT 1u  /* in: rank k   -> value of the entry of rank k, DSE_QUERY_NONE if k >= total */
+#define DSE_QUERY_NEXT   2u  /* in: value x  -> smallest entry value > x, DSE_QUERY_NONE if none */
+#define DSE_QUERY_PREV   3u  /* in: value x  -> largest entry value < x, DSE_QUERY_NONE if none */
+#define DSE_QUERY_TEST   4u  /* in: value x  -> 1 if x is an entry's value, else 0 (even x, x < 3, x outside the range: 0) */
+
+/* Bytes of the rank index of a range of nbits candidates (host arithmetic only). */
+uint64_t dse_query_index_bytes(uint64_t nbits);
+
+/* Build the index of a caller-owned device mask into caller-owned device memory, async on stream:
+ * index_dev[t], t = 0 .. tiles (tiles = ceil(nbits / 16384)), is the number of entries in the
+ * tiles before t, so index_dev[tiles] is the total. What lies behind those words, up to
+ * dse_query_index_bytes(nbits), is the library's. Bits past nbits in the last word are ignored.
+ * DSE_EINVAL for a null ctx or index, a null mask with nbits > 0, a misaligned index (8 bytes), or
+ * index_bytes below dse_query_index_bytes(nbits). DSE_ERANGE for a range beyond 2^62 or more than
+ * 2^44 candidates in one call. */
+int32_t dse_query_index_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                                  const uint64_t *mask_dev, uint64_t *index_dev, uint64_t index_bytes,
+                                  void *stream);
+
+/* out_dev[i] = the answer of `kind` to q_dev[i], i < nq, async on stream; index_dev as built by
+ * dse_query_index_dev_async for the same range and mask. Queries come in any order, duplicates
+ * allowed. Nothing outside [out_dev, out_dev + nq) is written; nq = 0 launches nothing. Bits past
+ * nbits in the last word are ignored; nbits = 0 is legal (rank 0, everything else
+ * DSE_QUERY_NONE or 0). DSE_QUERY_TEST reads no index: index_dev may be NULL for it. DSE_EINVAL
+ * for a null ctx, an unknown kind, null q_dev or out_dev with nq > 0, a null mask with nbits > 0,
+ * a null index for a kind that needs it, or a pointer that is not 8-byte aligned. DSE_ERANGE as
+ * above. */
+int32_t dse_query_dev_async(dse_ctx *ctx, uint32_t kind, uint64_t g_start, uint64_t nbits,
+                            const uint64_t *mask_dev, const uint64_t *index_dev,
+                            const uint64_t *q_dev, uint64_t nq, uint64_t *out_dev, void *stream);
+
+/* gen-table + sieve-e + index + queries of an odd-index range, on the first device; host arrays.
+ * The range rules of dse_sieve_odd_range apply. DSE_ENOMEM when the device buffers for nq queries
+ * and answers cannot be had. */
+int32_t dse_query_range(dse_ctx *ctx, uint32_t kind, uint64_t g_start, uint64_t nbits,
+                        const uint64_t *q, uint64_t nq, uint64_t *out);
+
+/* Queries against chunk my_num left resident by the last dse_sieve_all; my_num = 0: against all P
+ * chunks as the one range [3, 3 + 2 P cs) (dse_stats_resident's convention; the dropped tail is in
+ * no mask and in no answer). A chunk's index is built on its own device and stream by the first
+ * call that needs it and kept until dse_sieve_all replaces the masks or dse_destroy. For all
+ * chunks the host routes each query to the chunk that holds its candidate (its rank, for
+ * DSE_QUERY_SELECT), enqueues every chunk's batch on its device's stream before it waits for any,
+ * and completes the answers from the chunks' totals and first and last entries. DSE_EINVAL if the
+ * chunk is not resident. */
+int32_t dse_query_resident(dse_ctx *ctx, int32_t my_num, uint32_t kind,
+                           const uint64_t *q, uint64_t nq, uint64_t *out);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -385,6 +443,9 @@ int32_t dse_stats_merge(const dse_stats *a, const dse_stats *b, dse_stats *out);
  *   "stats_grid" = k in 1..1024: the dse_stats_* launches use at most k
  *   workgroups, so one workgroup walks several tiles and the closing launch
  *   sums several slabs on tiny inputs; 0 = default (3 per compute unit).
+ *   "query_grid" = k in 1..1024: the dse_query_* launches use at most k
+ *   workgroups, so a wave takes several queries on tiny inputs; 0 = default
+ *   (8 per compute unit).
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -395,7 +456,10 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   "table_local_builds": base tables built on a device of their own instead
  *   of broadcast (one per device and call);
  *   "primes_tile_bits": candidates per tile of the dse_primes_* kernels;
- *   "stats_tile_bits": candidates per tile of the dse_stats_* kernels.
+ *   "stats_tile_bits": candidates per tile of the dse_stats_* kernels;
+ *   "query_index_builds": rank indices dse_query_resident has built for
+ *   resident chunks so far (one per chunk and dse_sieve_all that replaced the
+ *   masks).
  * The "plan_*" names describe what the context's most recent sieving entry
  * point (dse_sieve_odd_range, dse_sieve_chunk, dse_sieve_all, dse_sieve_window,
  * dse_sieve_range_dev_async, and the calls that sieve a range before they
@@ -462,6 +526,13 @@ int32_t dse_debug_primes_word(uint64_t word, uint64_t g_word_start, uint64_t ran
  * dse_stats_dev_async for the mask, the patterns and the range. */
 int32_t dse_debug_stats_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits,
                              const uint32_t *patterns, uint32_t npatterns, dse_stats *out);
+
+/* The dse_query_* kernel's own per-word and per-tile bodies, run on the host over
+ * a host mask (no device call): the same answers as dse_query_index_dev_async +
+ * dse_query_dev_async on the same bits. Test-only; DSE_EINVAL / DSE_ERANGE as
+ * dse_query_dev_async for the kind, the pointers and the range. */
+int32_t dse_debug_query_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, uint32_t kind,
+                             const uint64_t *q, uint64_t nq, uint64_t *out);
 
 #ifdef __cplusplus
 }
