@@ -1,0 +1,294 @@
+// dse_goldbach_host.cpp -- minimal Goldbach partitions of a mask, the host side
+// (include/dse.h): a device-resident mask and the candidates below it become one
+// dse_goldbach on the device (dse_goldbach.hip), in the caller's device memory
+// (dse_goldbach_dev_async) or on the host (dse_goldbach_range,
+// dse_goldbach_resident); dse_goldbach_merge joins the results of adjacent ranges
+// by host arithmetic, and dse_debug_goldbach_host runs the kernel's per-word
+// bodies (dse_goldbach_word.h) on the host.
+#include <algorithm>
+#include <cstring>
+
+#include "dse_goldbach_word.h"
+#include "dse_host.h"
+
+using namespace dse;
+
+static_assert(sizeof(dse_goldbach) == 8 * DSE_GOLDBACH_WORDS, "dse_goldbach has no padding");
+static_assert(DSE_GOLDBACH_WORDS == kGbWords && DSE_GOLDBACH_PRIMES == kGbPrimes && DSE_GOLDBACH_NONE == kGbNone,
+              "the kernels write the struct of include/dse.h");
+
+namespace {
+
+// nprimes of a call -> the ranks it uses (0: all); DSE_EINVAL above DSE_GOLDBACH_PRIMES
+int32_t gb_nprimes(uint32_t nprimes, uint32_t* n) {
+  if (nprimes > DSE_GOLDBACH_PRIMES) return fail(DSE_EINVAL, "nprimes above 2048");
+  *n = nprimes ? nprimes : DSE_GOLDBACH_PRIMES;
+  return DSE_OK;
+}
+
+int32_t gb_check_below(const uint64_t* below, uint32_t below_shift, uint64_t below_bits, uint64_t g_start) {
+  if (below_shift > 63) return fail(DSE_EINVAL, "below_shift above 63");
+  if (below_bits > g_start) return fail(DSE_EINVAL, "below_bits reaches below candidate 0");
+  if (below_bits && !below) return fail(DSE_EINVAL, "null below with below_bits > 0");
+  if (reinterpret_cast<uintptr_t>(below) & 7u) return fail(DSE_EINVAL, "below is not 8-byte aligned");
+  return DSE_OK;
+}
+
+// whole words of a `below` of `bits` candidates that starts `shift` bits into its first word
+inline uint64_t below_words(uint32_t shift, uint64_t bits) { return (shift + bits + 63) / 64; }
+
+// Acquire the device's scratch for `stream`: the slabs of `grid` workgroups, behind them
+// `nres` results and `ncopy` copies of a neighbour's tail of `copy_words` words each.
+int32_t gb_acquire(DevState& d, uint32_t grid, uint32_t nres, uint32_t ncopy, uint64_t copy_words, hipStream_t stream,
+                   uint64_t** res, uint64_t** copies) {
+  StreamScratch& s = d.goldbach_scratch;
+  const uint64_t slabs = goldbach_scratch_bytes(grid);
+  const uint64_t need = slabs + (uint64_t)nres * sizeof(dse_goldbach) + (uint64_t)ncopy * copy_words * 8;
+  HIP_TRY(acquire_scratch_roomy(&s, need, stream));
+  char* const p = static_cast<char*>(s.buf.ptr) + slabs;
+  if (res) *res = reinterpret_cast<uint64_t*>(p);
+  if (copies) *copies = reinterpret_cast<uint64_t*>(p + (uint64_t)nres * sizeof(dse_goldbach));
+  return DSE_OK;
+}
+
+// the results at `res` to the host; drains d.stream and releases the scratch
+int32_t gb_collect(DevState& d, const uint64_t* res, uint32_t n, dse_goldbach* out) {
+  hipError_t e = hipMemcpyAsync(out, res, (uint64_t)n * sizeof(dse_goldbach), hipMemcpyDeviceToHost, d.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+  const hipError_t r = release_scratch(&d.goldbach_scratch, d.stream);
+  if (e == hipSuccess) e = r;
+  if (e != hipSuccess) return fail(DSE_EHIP, std::string("goldbach copy failed: ") + hipGetErrorString(e));
+  return DSE_OK;
+}
+
+void gb_empty(dse_goldbach* r, uint64_t g_start, uint64_t nbits, uint32_t n) {
+  std::memset(r, 0, sizeof *r);
+  r->g_start = g_start;
+  r->nbits = nbits;
+  r->nprimes = n;
+  r->first_unresolved = r->max_rank = r->max_c = DSE_GOLDBACH_NONE;
+}
+
+}  // namespace
+
+extern "C" uint64_t dse_goldbach_prime(uint32_t i) { return i < kGbPrimes ? 3ull + 2ull * kGbTable.h(i) : 0ull; }
+
+extern "C" uint64_t dse_goldbach_reach(uint32_t nprimes) {
+  if (nprimes > kGbPrimes) return 0;
+  return kGbTable.h((nprimes ? nprimes : kGbPrimes) - 1);
+}
+
+extern "C" int32_t dse_goldbach_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
+                                          const uint64_t* below_dev, uint32_t below_shift, uint64_t below_bits,
+                                          uint32_t nprimes, dse_goldbach* out_dev, void* stream) {
+  if (!ctx || !out_dev) return fail(DSE_EINVAL, "null ctx or out");
+  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
+  if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(mask_dev) & 7u) return fail(DSE_EINVAL, "mask_dev is not 8-byte aligned");
+  int32_t rc;
+  uint32_t n;
+  if ((rc = gb_nprimes(nprimes, &n))) return rc;
+  if ((rc = gb_check_below(below_dev, below_shift, below_bits, g_start))) return rc;
+  if ((rc = check_mask_range("goldbach", g_start, nbits))) return rc;
+  DevState& d = ctx->devs[0];
+  HIP_TRY(hipSetDevice(d.device));
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t grid = goldbach_grid(nbits, d.num_cus, ctx->goldbach_grid);
+  if ((rc = gb_acquire(d, grid, 0, 0, 0, s, nullptr, nullptr))) return rc;
+  const hipError_t e = launch_goldbach(g_start, nbits, mask_dev, 0, below_dev, below_shift, below_bits, n,
+                                       reinterpret_cast<uint64_t*>(out_dev), d.goldbach_scratch.buf.ptr, grid, s);
+  HIP_TRY(release_scratch(&d.goldbach_scratch, s));  // also after a failure: what was launched may read the scratch
+  if (e != hipSuccess) return fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
+  return DSE_OK;
+}
+
+extern "C" int32_t dse_goldbach_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, uint32_t nprimes,
+                                      dse_goldbach* out) {
+  if (!ctx || !out) return fail(DSE_EINVAL, "null ctx or out");
+  int32_t rc;
+  uint32_t n;
+  if ((rc = gb_nprimes(nprimes, &n))) return rc;
+  if ((rc = check_mask_range("goldbach", g_start, nbits))) return rc;
+  // the extended range: what the small primes can reach below g_start is sieved with it
+  const uint64_t reach = kGbTable.h(n - 1);
+  const uint64_t ext = nbits ? std::min(g_start, reach) : 0;
+  if ((rc = check_mask_range("goldbach", g_start - ext, nbits + ext))) return rc;
+  DevState& d = ctx->devs[0];
+  if (nbits && (rc = sieve_range_host(ctx, d, g_start - ext, nbits + ext, nullptr, nullptr, true))) return rc;
+  HIP_TRY(hipSetDevice(d.device));
+  // one scratch mask: `below` is its first ext bits, the range's own mask starts ext bits in
+  const uint64_t* const m = d.scratch_mask.as<uint64_t>();
+  const uint32_t grid = goldbach_grid(nbits, d.num_cus, ctx->goldbach_grid);
+  uint64_t* res;
+  if ((rc = gb_acquire(d, grid, 1, 0, 0, d.stream, &res, nullptr))) return rc;
+  const hipError_t e = launch_goldbach(g_start, nbits, m + (ext >> 6), (uint32_t)(ext & 63), m, 0, ext, n, res,
+                                       d.goldbach_scratch.buf.ptr, grid, d.stream);
+  if (e != hipSuccess) {
+    (void)release_scratch(&d.goldbach_scratch, d.stream);
+    return fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
+  }
+  dse_goldbach tmp;
+  if ((rc = gb_collect(d, res, 1, &tmp))) return rc;
+  *out = tmp;
+  return DSE_OK;
+}
+
+extern "C" int32_t dse_goldbach_resident(dse_ctx* ctx, int32_t my_num, uint32_t nprimes, dse_goldbach* out) {
+  if (!ctx || !out) return fail(DSE_EINVAL, "null ctx or out");
+  int32_t rc;
+  uint32_t n;
+  if ((rc = gb_nprimes(nprimes, &n))) return rc;
+  const ResidentSet& r = ctx->resident;
+  if (!r.valid || my_num < 0 || my_num > r.P)
+    return fail(DSE_EINVAL, "chunk " + std::to_string(my_num) + " is not resident");
+  const uint64_t cs = (uint64_t)r.cs;
+  const int32_t k0 = my_num ? my_num : 1, k1 = my_num ? my_num : r.P;
+  if ((rc = check_mask_range("goldbach", (uint64_t)(k1 - 1) * cs, cs))) return rc;
+  // chunk k > 1 sees the last `reach` candidates of chunk k - 1
+  const uint64_t reach = kGbTable.h(n - 1);
+  if (k1 > 1 && cs < reach)
+    return fail(DSE_EINVAL, "chunks of " + std::to_string(cs) + " candidates are shorter than the reach " +
+                                std::to_string(reach) + " of " + std::to_string(n) + " primes: lower nprimes");
+  const uint64_t off = cs - (k1 > 1 ? reach : 0);                          // the tail's first bit in a chunk's mask
+  const uint32_t tail_shift = (uint32_t)(off & 63);
+  const uint64_t tail_words = k1 > 1 ? below_words(tail_shift, reach) : 0;  // through the mask's last word
+
+  // every device's launches are enqueued on its stream before any result is waited for
+  const size_t nd = ctx->devs.size();
+  std::vector<std::vector<int32_t>> chunk(nd);
+  for (int32_t k = k0; k <= k1; ++k) chunk[(size_t)(k - 1) % nd].push_back(k);
+  std::vector<uint64_t*> res(nd, nullptr);
+  std::vector<bool> queued(nd, false);
+  rc = DSE_OK;
+  for (size_t i = 0; i < nd && !rc; ++i) {
+    if (chunk[i].empty()) continue;
+    DevState& d = ctx->devs[i];
+    if (hipSetDevice(d.device) != hipSuccess) {
+      rc = fail(DSE_EHIP, "hipSetDevice failed");
+      break;
+    }
+    const uint32_t cnt = (uint32_t)chunk[i].size();
+    const uint32_t grid = goldbach_grid(cs, d.num_cus, ctx->goldbach_grid);
+    uint64_t* copies = nullptr;
+    if ((rc = gb_acquire(d, grid, cnt, nd > 1 ? cnt : 0, tail_words, d.stream, &res[i], &copies))) break;
+    queued[i] = true;
+    hipError_t e = hipSuccess;
+    for (uint32_t j = 0; j < cnt && e == hipSuccess; ++j) {
+      const int32_t k = chunk[i][j];
+      const uint64_t* below = nullptr;
+      uint64_t below_bits = 0;
+      if (k > 1 && reach) {
+        const size_t src = (size_t)(k - 2) % nd;
+        const uint64_t* const tail = r.masks[k - 2].as<uint64_t>() + (off >> 6);
+        below_bits = reach;
+        if (src == i) {
+          below = tail;  // the neighbour's mask is this device's: a pointer into it
+        } else {
+          // the neighbour's whole words into this device's scratch, on this device's stream: the
+          // launch behind it is ordered by the stream, the scratch's next user by its event
+          uint64_t* const dst = copies + (uint64_t)j * tail_words;
+          const DevState& sd = ctx->devs[src];
+          e = sd.device == d.device
+                  ? hipMemcpyAsync(dst, tail, tail_words * 8, hipMemcpyDeviceToDevice, d.stream)
+                  : hipMemcpyPeerAsync(dst, d.device, tail, sd.device, tail_words * 8, d.stream);
+          below = dst;
+        }
+      }
+      if (e == hipSuccess)
+        e = launch_goldbach((uint64_t)(k - 1) * cs, cs, r.masks[k - 1].as<uint64_t>(), 0, below, tail_shift, below_bits,
+                            n, res[i] + (uint64_t)j * DSE_GOLDBACH_WORDS, d.goldbach_scratch.buf.ptr, grid, d.stream);
+    }
+    if (e != hipSuccess) rc = fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
+  }
+  std::vector<dse_goldbach> parts((size_t)(k1 - k0 + 1));
+  std::vector<dse_goldbach> got;
+  for (size_t i = 0; i < nd; ++i) {  // collect what was enqueued, also after a failure: the scratch must be released
+    if (!queued[i]) continue;
+    DevState& d = ctx->devs[i];
+    (void)hipSetDevice(d.device);
+    got.resize(chunk[i].size());
+    const int32_t r2 = gb_collect(d, res[i], (uint32_t)chunk[i].size(), got.data());
+    if (r2 && !rc) rc = r2;
+    if (!r2)
+      for (size_t j = 0; j < got.size(); ++j) parts[(size_t)(chunk[i][j] - k0)] = got[j];
+  }
+  if (rc) return rc;
+  dse_goldbach acc = parts[0];
+  for (size_t j = 1; j < parts.size(); ++j)
+    if ((rc = dse_goldbach_merge(&acc, &parts[j], &acc))) return rc;
+  *out = acc;
+  return DSE_OK;
+}
+
+extern "C" int32_t dse_goldbach_merge(const dse_goldbach* a, const dse_goldbach* b, dse_goldbach* out) {
+  if (!a || !b || !out) return fail(DSE_EINVAL, "null goldbach result");
+  if (a->g_start + a->nbits != b->g_start || a->g_start > b->g_start)
+    return fail(DSE_EINVAL, "the ranges are not adjacent");
+  if (a->nprimes != b->nprimes || a->nprimes < 1 || a->nprimes > DSE_GOLDBACH_PRIMES)
+    return fail(DSE_EINVAL, "the results are of different nprimes");
+  if (b->g_start > (1ull << 62) || b->nbits > (1ull << 62) - b->g_start)
+    return fail(DSE_ERANGE, "merged range beyond 2^62");
+  dse_goldbach r;  // out may alias a or b
+  r.g_start = a->g_start;
+  r.nbits = a->nbits + b->nbits;
+  r.nprimes = a->nprimes;
+  r.resolved = a->resolved + b->resolved;
+  r.unresolved = a->unresolved + b->unresolved;
+  r.first_unresolved = a->first_unresolved != DSE_GOLDBACH_NONE ? a->first_unresolved : b->first_unresolved;
+  const bool take_b =
+      b->max_rank != DSE_GOLDBACH_NONE && (a->max_rank == DSE_GOLDBACH_NONE || b->max_rank > a->max_rank);
+  r.max_rank = take_b ? b->max_rank : a->max_rank;
+  r.max_c = take_b ? b->max_c : a->max_c;
+  for (uint32_t i = 0; i < DSE_GOLDBACH_PRIMES; ++i) r.hist[i] = a->hist[i] + b->hist[i];
+  *out = r;
+  return DSE_OK;
+}
+
+extern "C" int32_t dse_debug_goldbach_host(const uint64_t* mask, uint64_t g_start, uint64_t nbits, const uint64_t* below,
+                                           uint32_t below_shift, uint64_t below_bits, uint32_t nprimes,
+                                           dse_goldbach* out) {
+  if (!out) return fail(DSE_EINVAL, "null out");
+  if (nbits && !mask) return fail(DSE_EINVAL, "null mask");
+  int32_t rc;
+  uint32_t n;
+  if ((rc = gb_nprimes(nprimes, &n))) return rc;
+  if ((rc = gb_check_below(below, below_shift, below_bits, g_start))) return rc;
+  if ((rc = check_mask_range("goldbach", g_start, nbits))) return rc;
+  const GbSrc src{mask, below, nbits, below_bits, 0u, below_shift};
+  dse_goldbach r;
+  gb_empty(&r, g_start, nbits, n);
+  // the main kernel's tile loop, one tile's line at a time
+  std::vector<uint64_t> line(kGbLineWords + 1);
+  const uint32_t* const l32 = reinterpret_cast<const uint32_t*>(line.data());
+  auto ld = [&](uint32_t k) { return l32[k]; };
+  uint64_t br = kGbNone, bc = kGbNone;
+  for (uint64_t t = 0; t < mask_tiles(nbits); ++t) {
+    for (uint32_t k = 0; k < kGbLineWords; ++k)
+      line[k] = gb_bits64(src, ((int64_t)(t * kMaskTileWords) - (int64_t)kGbLowWords + (int64_t)k) * 64);
+    for (uint32_t tid = 0; tid < kMaskTileWords; ++tid) {
+      const uint64_t wi = t * kMaskTileWords + tid, pos0 = wi * 64;
+      const uint32_t d0 = 2u * (kGbLowWords + tid);
+      auto hit_at = [&](uint32_t i, uint64_t hit) {
+        if (!hit) return;
+        r.hist[i] += (uint64_t)__builtin_popcountll(hit);
+        const uint64_t c = pos0 + (uint32_t)__builtin_ctzll(hit);
+        if (gb_better(i, c, br, bc)) {
+          br = i;
+          bc = c;
+        }
+      };
+      uint64_t U = gb_search_first<kGbRegRanks>(gb_evens(nbits, wi), n, d0, ld, hit_at);
+      U = gb_search(U, kGbTable, kGbRegRanks, n, d0, ld, [](uint64_t u) { return u != 0; }, hit_at);
+      if (U) {
+        r.unresolved += (uint64_t)__builtin_popcountll(U);
+        if (r.first_unresolved == DSE_GOLDBACH_NONE) r.first_unresolved = g_start + pos0 + (uint32_t)__builtin_ctzll(U);
+      }
+    }
+  }
+  // the closing kernel's scalar members
+  r.resolved = nbits - r.unresolved;
+  r.max_rank = br;
+  if (br != kGbNone) r.max_c = g_start + bc;
+  *out = r;
+  return DSE_OK;
+}

@@ -469,6 +469,7 @@ const struct {
      [](dse_ctx* c, int64_t v) { c->primes_slab_entries = (uint64_t)v; }},
     {"stats_grid", 0, (int64_t)kStatsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->stats_grid = (uint32_t)v; }},
     {"query_grid", 0, (int64_t)kQueryMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->query_grid = (uint32_t)v; }},
+    {"goldbach_grid", 0, (int64_t)kGbMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->goldbach_grid = (uint32_t)v; }},
 };
 
 }  // namespace
@@ -580,6 +581,7 @@ void dse_destroy(dse_ctx* ctx) {
     (void)free_scratch(&d.primes_sums);
     (void)free_scratch(&d.stats_scratch);
     (void)free_scratch(&d.query_scratch);
+    (void)free_scratch(&d.goldbach_scratch);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }

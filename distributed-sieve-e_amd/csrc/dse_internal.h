@@ -1,9 +1,10 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
-// dse_primes.hip, dse_stats.hip, dse_query.hip) and the C-ABI host layer (dse_host.cpp,
-// dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp, dse_query_host.cpp). Not installed;
+// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip) and the C-ABI host layer (dse_host.cpp,
+// dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp, dse_query_host.cpp,
+// dse_goldbach_host.cpp). Not installed;
 // include/dse.h is the ABI. The units that read a resident mask (finish,
-// primes, stats, query) share its range, tiles and clipped word load (dse_mask.h);
+// primes, stats, query, goldbach) share its range, tiles and clipped word load (dse_mask.h);
 // every unit with a workgroup sum or scan takes it from dse_block.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -263,5 +264,21 @@ uint64_t query_index_words(uint64_t nbits);
 uint32_t query_grid(uint32_t kind, uint64_t nq, int num_cus, uint32_t grid_cap);
 hipError_t launch_query(uint32_t kind, uint64_t g_start, uint64_t nbits, const uint64_t* mask, const void* index,
                         const uint64_t* q, uint64_t nq, uint64_t* out, uint32_t grid, hipStream_t stream);
+
+// Minimal Goldbach partitions of a mask (dse_goldbach.hip): the main launch over `grid`
+// workgroups, each walking its own run of tiles of kMaskTileBits candidates, and the closing
+// launch, which writes the dse_goldbach (kGbWords uint64 words) at `out`. The range's candidates
+// are the bits of `mask` from bit mask_shift on (0 for a caller's mask; dse_goldbach_range's lies
+// behind its `below` in one scratch mask), the below_bits candidates below it the bits of `below`
+// from bit below_shift on; nprimes in 1..2048. grid = goldbach_grid(nbits, CUs of the device, cap
+// or 0): 0 exactly for an empty range, at most kGbMaxGrid. slabs:
+// goldbach_scratch_bytes(grid) bytes of device scratch.
+constexpr uint32_t kGbMaxGrid = 1024;
+constexpr uint32_t kGbWords = 8 + 2048;
+uint32_t goldbach_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
+uint64_t goldbach_scratch_bytes(uint32_t grid);
+hipError_t launch_goldbach(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint32_t mask_shift,
+                           const uint64_t* below, uint32_t below_shift, uint64_t below_bits, uint32_t nprimes,
+                           uint64_t* out, void* slabs, uint32_t grid, hipStream_t stream);
 
 }  // namespace dse

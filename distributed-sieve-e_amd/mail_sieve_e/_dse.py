@@ -31,6 +31,9 @@ PRIMES_TILE_BITS = 256 * 64
 # include/dse.h dse_stats as uint64 words, and where its members start
 STATS_WORDS, STATS_GAP_BINS, STATS_MAX_PATTERNS, STATS_NONE = 27 + 1024, 1024, 8, (1 << 64) - 1
 
+# include/dse.h dse_goldbach as uint64 words: 8 scalar members, then hist[2048]
+GOLDBACH_PRIMES, GOLDBACH_WORDS, GOLDBACH_NONE = 2048, 8 + 2048, (1 << 64) - 1
+
 # include/dse.h DSE_QUERY_*
 QUERY_NONE = (1 << 64) - 1
 QUERY_RANK, QUERY_SELECT, QUERY_NEXT, QUERY_PREV, QUERY_TEST = range(5)
@@ -83,6 +86,13 @@ SIGNATURES = {
     "dse_query_dev_async": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "dse_query_range": (_i32, [_vp, _u32, _u64, _u64, _pu64, _u64, _pu64]),
     "dse_query_resident": (_i32, [_vp, _i32, _u32, _pu64, _u64, _pu64]),
+    "dse_goldbach_prime": (_u64, [_u32]),
+    "dse_goldbach_reach": (_u64, [_u32]),
+    "dse_goldbach_dev_async": (_i32, [_vp, _u64, _u64, _vp, _vp, _u32, _u64, _u32, _vp, _vp]),
+    "dse_goldbach_range": (_i32, [_vp, _u64, _u64, _u32, _pu64]),
+    "dse_goldbach_resident": (_i32, [_vp, _i32, _u32, _pu64]),
+    "dse_goldbach_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_debug_goldbach_host": (_i32, [_pu64, _u64, _u64, _pu64, _u32, _u64, _u32, _pu64]),
     "dse_debug_query_host": (_i32, [_pu64, _u64, _u64, _u32, _pu64, _u64, _pu64]),
     "dse_debug_stats_host": (_i32, [_pu64, _u64, _u64, _pu32, _u32, _pu64]),
     "dse_debug_finish_format": (_i32, [_u64, ctypes.c_uint32, ctypes.c_char_p]),

@@ -133,6 +133,77 @@ def stats_host(mask: np.ndarray, g_start: int, nbits: int, patterns=CONSTELLATIO
     return Stats(out)
 
 
+class Goldbach:
+    """One dse_goldbach (include/dse.h "additive questions"): the minimal Goldbach
+    partitions of the evens 6 + 2c of the odd candidates [g_start, g_start +
+    nbits). ``words`` is the struct as its uint64 words."""
+
+    def __init__(self, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.shape != (_dse.GOLDBACH_WORDS,):
+            raise ValueError("a dse_goldbach is %d uint64 words" % _dse.GOLDBACH_WORDS)
+        self.words = w
+
+    @staticmethod
+    def _opt(v):
+        return None if v == _dse.GOLDBACH_NONE else v
+
+    g_start = property(lambda s: int(s.words[0]))
+    nbits = property(lambda s: int(s.words[1]))
+    nprimes = property(lambda s: int(s.words[2]))
+    resolved = property(lambda s: int(s.words[3]))
+    unresolved = property(lambda s: int(s.words[4]))
+    first_unresolved = property(lambda s: Goldbach._opt(int(s.words[5])))
+    max_rank = property(lambda s: Goldbach._opt(int(s.words[6])))
+    max_c = property(lambda s: Goldbach._opt(int(s.words[7])))
+
+    @property
+    def hist(self) -> np.ndarray:
+        """uint64[2048]: hist[i] = evens whose minimal partition uses the i-th odd prime."""
+        return self.words[8:8 + _dse.GOLDBACH_PRIMES]
+
+    @property
+    def first_unresolved_even(self) -> Optional[int]:
+        """The lowest even of the range with no partition among the primes used, or None."""
+        return None if self.first_unresolved is None else 6 + 2 * self.first_unresolved
+
+    @property
+    def max_prime(self) -> Optional[int]:
+        """The largest minimal prime over the resolved evens, or None."""
+        return None if self.max_rank is None else int(lib().dse_goldbach_prime(self.max_rank))
+
+    @property
+    def max_even(self) -> Optional[int]:
+        """The first even whose minimal prime is ``max_prime``, or None."""
+        return None if self.max_c is None else 6 + 2 * self.max_c
+
+    def merge(self, other: "Goldbach") -> "Goldbach":
+        """The result of this range followed by the adjacent ``other`` (dse_goldbach_merge)."""
+        out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
+        check(lib().dse_goldbach_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_goldbach_merge")
+        return Goldbach(out)
+
+    def __eq__(self, other):
+        return isinstance(other, Goldbach) and np.array_equal(self.words, other.words)
+
+    def __repr__(self):
+        return (f"Goldbach(g_start={self.g_start}, nbits={self.nbits}, nprimes={self.nprimes}, "
+                f"unresolved={self.unresolved}, max_prime={self.max_prime} at {self.max_even})")
+
+
+def goldbach_host(mask: np.ndarray, g_start: int, nbits: int, below: Optional[np.ndarray] = None,
+                  below_shift: int = 0, below_bits: int = 0, nprimes: int = 0) -> Goldbach:
+    """Test-only: the Goldbach kernel's per-word bodies run on the host over a host
+    mask and a host ``below`` (include/dse.h dse_debug_goldbach_host)."""
+    out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    b = None if below is None else np.ascontiguousarray(below, dtype=np.uint64)
+    check(lib().dse_debug_goldbach_host(u64p(m) if len(m) else None, g_start, nbits,
+                                        u64p(b) if b is not None and len(b) else None, below_shift, below_bits,
+                                        nprimes, u64p(out)), "dse_debug_goldbach_host")
+    return Goldbach(out)
+
+
 class Context:
     """A libdse context: one process driving ``num_gpus`` devices, or one
     device (``device=``) for one-process-per-GPU ranks. ``logical=k`` (tests
@@ -350,6 +421,44 @@ class Context:
         b = hi if hi & 1 else hi - 1
         return self.stats_range((a - 3) // 2, (b - a) // 2 + 1, patterns)
 
+
+    # -- additive questions -------------------------------------------------------
+    def goldbach_dev_async(self, g_start: int, nbits: int, mask_ptr: int, below_ptr: int, below_shift: int,
+                           below_bits: int, nprimes: int, out_ptr: int, stream_ptr: int = 0):
+        """The minimal Goldbach partitions of a device mask as one dse_goldbach
+        (_dse.GOLDBACH_WORDS uint64 words) in device memory at out_ptr; the
+        below_bits candidates below g_start are the bits from below_shift on of
+        the device bit string at below_ptr (include/dse.h dse_goldbach_dev_async)."""
+        check(lib().dse_goldbach_dev_async(self.ptr, g_start, nbits, mask_ptr or None, below_ptr or None, below_shift,
+                                           below_bits, nprimes, out_ptr or None, stream_ptr or None),
+              "dse_goldbach_dev_async")
+
+    def goldbach_range(self, g_start: int, nbits: int, nprimes: int = 0) -> Goldbach:
+        """gen-table + sieve-e of an odd-index range (and of what the small primes
+        reach below it) and the minimal Goldbach partitions of its evens 6 + 2c,
+        computed on the device: only the dse_goldbach reaches the host."""
+        out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
+        check(lib().dse_goldbach_range(self.ptr, g_start, nbits, nprimes, u64p(out)), "dse_goldbach_range")
+        return Goldbach(out)
+
+    def goldbach_window(self, lo: int, hi: int, nprimes: int = 0) -> Goldbach:
+        """The minimal Goldbach partitions of the evens in [max(lo, 6), hi]; an
+        empty window gives the empty result."""
+        a = max(lo, 6)
+        a += a & 1
+        b = hi - (hi & 1)
+        if b < a:
+            return self.goldbach_range(min((a - 6) // 2, 1 << 62), 0, nprimes)
+        return self.goldbach_range((a - 6) // 2, (b - a) // 2 + 1, nprimes)
+
+    def resident_goldbach(self, my_num: Optional[int] = None, nprimes: int = 0) -> Goldbach:
+        """The minimal Goldbach partitions of a chunk the last sieve_all left on
+        its device (it sees the tail of the chunk before it), or (my_num=None) of
+        all its chunks: the per-chunk results merged in order."""
+        out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
+        check(lib().dse_goldbach_resident(self.ptr, 0 if my_num is None else my_num, nprimes, u64p(out)),
+              "dse_goldbach_resident")
+        return Goldbach(out)
 
     # -- rank and select ---------------------------------------------------------
     def query_index_dev_async(self, g_start: int, nbits: int, mask_ptr: int, index_ptr: int, index_bytes: int,

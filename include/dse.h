@@ -402,6 +402,87 @@ int32_t dse_query_range(dse_ctx *ctx, uint32_t kind, uint64_t g_start, uint64_t 
 int32_t dse_query_resident(dse_ctx *ctx, int32_t my_num, uint32_t kind,
                            const uint64_t *q, uint64_t nq, uint64_t *out);
 
+/* ---- additive questions ---------------------------------------------------- */
+
+/* Minimal Goldbach partitions, computed on the GPU from a device-resident mask; only the
+ * dse_goldbach crosses to the host.
+ *
+ * Evens. The even of candidate index c is e(c) = 6 + 2c = 3 + (3 + 2c), so a range [g_start,
+ * g_start + nbits) owns exactly nbits evens, adjacent ranges own adjacent evens, and [0, n) owns
+ * 6, 8, ..., 4 + 2n. The even 4 = 2 + 2 belongs to no range, as the prime 2 is in no mask.
+ *
+ * Small primes. P_i is the i-th odd prime (P_0 = 3) and h_i = (P_i - 3) / 2. A call uses the first
+ * nprimes of the DSE_GOLDBACH_PRIMES = 2048 (P_2047 = 17881, h_2047 = 8939); nprimes is 1..2048,
+ * and 0 means 2048. Its reach is h_(nprimes - 1): dse_goldbach_reach.
+ *
+ * Partition. e(c) - P_i = 3 + 2 (c - h_i), so partition i of e(c) holds iff candidate c - h_i is a
+ * visible entry (a set bit). The range's own candidates are visible, and so are the `below`
+ * candidates [g_start - below_bits, g_start) the caller supplies; anything lower, or below
+ * candidate 0, is not an entry. The minimal rank of e(c) is the smallest i < nprimes whose
+ * partition holds; with none, e(c) is unresolved. When all candidates down to 0 are visible the
+ * minimal p is automatically <= q.
+ *
+ * Every member is a uint64_t and there is no padding: bindings may treat a dse_goldbach as an array
+ * of DSE_GOLDBACH_WORDS uint64 words. */
+#define DSE_GOLDBACH_PRIMES 2048
+#define DSE_GOLDBACH_NONE UINT64_MAX
+#define DSE_GOLDBACH_WORDS (8 + DSE_GOLDBACH_PRIMES)
+typedef struct dse_goldbach {
+  uint64_t g_start, nbits;      /* the range the numbers are of */
+  uint64_t nprimes;             /* small primes used, 1..2048 */
+  uint64_t resolved, unresolved; /* resolved + unresolved == nbits */
+  uint64_t first_unresolved;    /* lowest global index c of an unresolved even, DSE_GOLDBACH_NONE if none */
+  uint64_t max_rank;            /* largest minimal rank over the resolved evens, DSE_GOLDBACH_NONE if none */
+  uint64_t max_c;               /* lowest global index c whose even attains it, DSE_GOLDBACH_NONE if none */
+  uint64_t hist[DSE_GOLDBACH_PRIMES]; /* hist[i] = evens whose minimal rank is i; slots >= nprimes are 0 */
+} dse_goldbach;
+
+/* P_i, the i-th odd prime (P_0 = 3); 0 for i >= DSE_GOLDBACH_PRIMES. */
+uint64_t dse_goldbach_prime(uint32_t i);
+
+/* h of the last of the first nprimes small primes (0 means 2048): how far below its own candidate
+ * an even's partitions look. Host arithmetic only; 0 for nprimes above 2048. */
+uint64_t dse_goldbach_reach(uint32_t nprimes);
+
+/* Async on stream, on a caller-owned device mask (bit c = candidate g_start + c). Candidate
+ * g_start - below_bits + j, j < below_bits, is bit below_shift + j of the bit string at below_dev:
+ * below_shift < 64, below_bits <= g_start, below_dev 8-byte aligned, NULL allowed when below_bits =
+ * 0. So `below` may be a pointer into a larger mask, with no copy. Only the whole words that cover
+ * those bits are read, and only the last dse_goldbach_reach(nprimes) of the bits can matter. Every
+ * member of *out_dev (sizeof(dse_goldbach) bytes of device memory, 8-byte aligned) is written and
+ * nothing outside it is touched. Bits past nbits in the last mask word are ignored; nbits = 0
+ * writes the empty result. DSE_EINVAL for a null ctx or out_dev, a null mask with nbits > 0, a
+ * misaligned mask_dev, below_dev or out_dev, nprimes > 2048, below_shift > 63, below_bits >
+ * g_start, or a null below_dev with below_bits > 0. DSE_ERANGE for a range beyond 2^62 or more than
+ * 2^44 candidates in one call. */
+int32_t dse_goldbach_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                               const uint64_t *mask_dev, const uint64_t *below_dev,
+                               uint32_t below_shift, uint64_t below_bits, uint32_t nprimes,
+                               dse_goldbach *out_dev, void *stream);
+
+/* gen-table + sieve-e + minimal partitions of an odd-index range, on the first device; host
+ * result. The range is sieved together with the min(g_start, reach) candidates below it, which the
+ * kernel sees as `below` (a pointer and a shift into the same scratch mask): every even of the
+ * range gets its true minimal partition. The range rules of dse_sieve_odd_range apply. */
+int32_t dse_goldbach_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, uint32_t nprimes,
+                           dse_goldbach *out);
+
+/* The same for chunk my_num left resident by the last dse_sieve_all; my_num = 0: for all P chunks,
+ * that is for [3, 3 + 2 P cs) (dse_stats_resident's convention). Chunk k > 1 sees the tail of chunk
+ * k - 1 as its `below`: a pointer into that mask when both are on one device, otherwise a copy of
+ * those whole words into this device's scratch. Every device's launches are enqueued on its own
+ * stream before any is waited for, and the results are merged on the host in chunk order.
+ * DSE_EINVAL if the chunk is not resident, and when a chunk that needs a `below` is shorter than
+ * dse_goldbach_reach(nprimes) (the message says so: lower nprimes). */
+int32_t dse_goldbach_resident(dse_ctx *ctx, int32_t my_num, uint32_t nprimes, dse_goldbach *out);
+
+/* The result of the union of two adjacent ranges, by host arithmetic only; out may alias a or b.
+ * Needs a->g_start + a->nbits == b->g_start and equal nprimes (else DSE_EINVAL; out is not
+ * touched); a union that ends above 2^62 gives DSE_ERANGE. Counts and the histogram add; the
+ * maximum keeps the first strictly greatest; first_unresolved is a's if a has one, otherwise b's.
+ * Each side must have been computed with the candidates below it visible (b's `below` = a's tail). */
+int32_t dse_goldbach_merge(const dse_goldbach *a, const dse_goldbach *b, dse_goldbach *out);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -446,6 +527,9 @@ int32_t dse_query_resident(dse_ctx *ctx, int32_t my_num, uint32_t kind,
  *   "query_grid" = k in 1..1024: the dse_query_* launches use at most k
  *   workgroups, so a wave takes several queries on tiny inputs; 0 = default
  *   (8 per compute unit).
+ *   "goldbach_grid" = k in 1..1024: the dse_goldbach_* launches use at most k
+ *   workgroups, so one workgroup walks several tiles and the closing launch
+ *   sums several slabs on tiny inputs; 0 = default (one resident round).
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -533,6 +617,15 @@ int32_t dse_debug_stats_host(const uint64_t *mask, uint64_t g_start, uint64_t nb
  * dse_query_dev_async for the kind, the pointers and the range. */
 int32_t dse_debug_query_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, uint32_t kind,
                              const uint64_t *q, uint64_t nq, uint64_t *out);
+
+/* The dse_goldbach_* kernel's own per-word bodies, run on the host in a plain loop
+ * over the tiles and words of a host mask and a host `below` (no device call): the
+ * same result as dse_goldbach_dev_async on the same bits. Test-only; DSE_EINVAL /
+ * DSE_ERANGE as dse_goldbach_dev_async for the pointers, nprimes, `below` and the
+ * range. */
+int32_t dse_debug_goldbach_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits,
+                                const uint64_t *below, uint32_t below_shift, uint64_t below_bits,
+                                uint32_t nprimes, dse_goldbach *out);
 
 #ifdef __cplusplus
 }
