@@ -1,6 +1,7 @@
 // dse_block.h -- wave and workgroup primitives of the gfx950 kernels (device
 // only): sums and inclusive scans by shuffles inside a wave of 64, the waves'
-// totals through one LDS word per wave, one barrier.
+// totals through one LDS word per wave, one barrier; the best of a pair under
+// a caller's order (block_best, two barriers).
 //
 // s_wave arguments are kThreads / 64 elements of LDS. A primitive writes them
 // before its barrier and reads them behind it, so a second call on the same
@@ -75,6 +76,35 @@ __device__ __forceinline__ T block_sum(T v, T* s_wave) {
 #pragma unroll
   for (uint32_t i = 0; i < kThreads / 64; ++i) sum += s_wave[i];
   return sum;
+}
+
+// The workgroup's best pair (a, b), in every thread: better(a', b', a, b) says whether (a', b')
+// comes before (a, b). s_a, s_b: kWaves elements of LDS each. Two barriers, the first before the
+// arrays are written (their last readers), so a second call needs no barrier in between.
+template <uint32_t kWaves, typename Better>
+__device__ __forceinline__ void block_best(uint64_t& a, uint64_t& b, unsigned long long* s_a, unsigned long long* s_b,
+                                           Better better) {
+  for (uint32_t o = 32; o > 0; o >>= 1) {
+    const uint64_t oa = (uint64_t)__shfl_xor((unsigned long long)a, o);
+    const uint64_t ob = (uint64_t)__shfl_xor((unsigned long long)b, o);
+    if (better(oa, ob, a, b)) {
+      a = oa;
+      b = ob;
+    }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63u) == 0) {
+    s_a[threadIdx.x >> 6] = a;
+    s_b[threadIdx.x >> 6] = b;
+  }
+  __syncthreads();
+  a = s_a[0];
+  b = s_b[0];
+  for (uint32_t i = 1; i < kWaves; ++i)
+    if (better(s_a[i], s_b[i], a, b)) {
+      a = s_a[i];
+      b = s_b[i];
+    }
 }
 
 // The single-workgroup scan over n values (tile or segment sums) by one

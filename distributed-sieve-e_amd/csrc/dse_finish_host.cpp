@@ -134,13 +134,9 @@ int32_t finish_check_range(uint32_t flags, uint64_t g_start, uint64_t nbits) {
 int32_t finish_launch(DevState& d, uint32_t flags, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
                       uint64_t first_rank, void* text_dev, uint64_t text_cap, unsigned long long* totals_dev,
                       hipStream_t stream) {
-  StreamScratch& sums = d.finish_sums;
-  HIP_TRY(acquire_scratch_roomy(&sums, finish_scratch_bytes(nbits), stream));
-  const hipError_t e = launch_finish_text(flags, g_start, nbits, mask_dev, first_rank, text_dev, text_cap,
-                                          totals_dev, sums.buf.ptr, stream);
-  HIP_TRY(release_scratch(&sums, stream));  // also after a failure: what was launched may read the scratch
-  if (e != hipSuccess) return fail(DSE_EHIP, std::string("launch_finish_text failed: ") + hipGetErrorString(e));
-  return DSE_OK;
+  return scratch_launch(d.finish_sums, finish_scratch_bytes(nbits), stream, "launch_finish_text", [&](void* sum) {
+    return launch_finish_text(flags, g_start, nbits, mask_dev, first_rank, text_dev, text_cap, totals_dev, sum, stream);
+  });
 }
 
 // The slab pipeline: mask_dev (ready in d.stream's order) -> file. Slab i+1 is

@@ -30,9 +30,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dse_block.h"
 #include "dse_goldbach_word.h"
 #include "dse_internal.h"
+#include "dse_slab.h"
 
 namespace dse {
 namespace {
@@ -51,8 +51,7 @@ static_assert(kGbRegRanks <= kGbPrimes && kGbTable.h(kGbRegRanks - 1) <= 64 * kG
 // a workgroup's slab, in uint64 words
 constexpr uint32_t kSlUnres = 0, kSlFirst = 1, kSlMaxR = 2, kSlMaxC = 3, kSlBins = 4, kSlHist = 8,
                    kSlabWords = kSlHist + kGbPrimes;
-// the closing kernel: one thread per slab, 64 bins per workgroup
-constexpr uint32_t kClThreads = 1024, kClBins = 64, kClGroups = kGbPrimes / kClBins;
+constexpr uint32_t kClThreads = kSlabCloseThreads, kClBins = kSlabCloseBins;
 static_assert(kGbMaxGrid <= kClThreads, "the closing kernel reads one slab per thread");
 
 // dse_goldbach as uint64 words
@@ -65,35 +64,16 @@ __constant__ GbTable c_gb_table = gb_make_table();
 
 struct GbArgs {
   GbSrc s;
-  uint64_t g_start, ntiles, tiles_per_wg;
+  uint64_t g_start;
+  SlabRun run;
   uint32_t nprimes;
 };
 
-// the workgroup's best (rank, candidate) in every thread (two barriers)
-template <uint32_t kWaves>
-__device__ __forceinline__ void gb_block_best(uint64_t& br, uint64_t& bc, unsigned long long* s_r,
-                                              unsigned long long* s_c) {
-  for (uint32_t o = 32; o > 0; o >>= 1) {
-    const uint64_t r = (uint64_t)__shfl_xor((unsigned long long)br, o);
-    const uint64_t c = (uint64_t)__shfl_xor((unsigned long long)bc, o);
-    if (r != kGbNone && gb_better(r, c, br, bc)) {
-      br = r;
-      bc = c;
-    }
-  }
-  __syncthreads();  // the arrays' last readers
-  if ((threadIdx.x & 63u) == 0) {
-    s_r[threadIdx.x >> 6] = br;
-    s_c[threadIdx.x >> 6] = bc;
-  }
-  __syncthreads();
-  br = s_r[0];
-  bc = s_c[0];
-  for (uint32_t i = 1; i < kWaves; ++i)
-    if (s_r[i] != kGbNone && gb_better(s_r[i], s_c[i], br, bc)) {
-      br = s_r[i];
-      bc = s_c[i];
-    }
+// block_best's order: a maximum beats none (gb_better alone would let kGbNone win by r > br). Two
+// returns: as one && expression it compiles to selects, another stream than the one measured.
+__device__ __forceinline__ bool gb_best_better(uint64_t r, uint64_t c, uint64_t br, uint64_t bc) {
+  if (r != kGbNone && gb_better(r, c, br, bc)) return true;
+  return false;
 }
 
 __global__ __launch_bounds__(kGbThreads) void gb_main_kernel(GbArgs a, unsigned long long* __restrict__ slabs) {
@@ -117,8 +97,8 @@ __global__ __launch_bounds__(kGbThreads) void gb_main_kernel(GbArgs a, unsigned 
   uint64_t unres = 0, first = kGbNone;  // this thread's unresolved evens and the first of them
   uint64_t br = kGbNone, bc = kGbNone;  // its largest minimal rank and the lowest candidate that has it
 
-  const uint64_t t0 = (uint64_t)blockIdx.x * a.tiles_per_wg;
-  const uint64_t t1 = min(a.ntiles, t0 + a.tiles_per_wg);
+  uint64_t t0, t1;
+  slab_tiles(a.run, t0, t1);
   // word k of tile t's line: the positions from 64 (256 t - kGbLowWords + k) on
   auto fetch = [&](uint64_t t, uint32_t k) {
     return gb_bits64(a.s, ((int64_t)(t * kMaskTileWords) - (int64_t)kGbLowWords + (int64_t)k) * 64);
@@ -196,11 +176,11 @@ __global__ __launch_bounds__(kGbThreads) void gb_main_kernel(GbArgs a, unsigned 
     if (lane == 0 && u) atomicAdd(&s_unres, (unsigned long long)u);
     if (first != kGbNone) atomicMin(&s_first, (unsigned long long)first);
   }
-  gb_block_best<kGbWaves>(br, bc, s_r, s_c);  // its barriers also make the LDS sums final
+  block_best<kGbWaves>(br, bc, s_r, s_c, gb_best_better);  // its barriers also make the LDS sums final
   if (br == kGbNone) {
     // nothing resolved at a later rank in the whole run: the maximum is among the first ranks
     walk(true);  // (the reduction's barriers: the first walk's last line is read no more)
-    gb_block_best<kGbWaves>(br, bc, s_r, s_c);
+    block_best<kGbWaves>(br, bc, s_r, s_c, gb_best_better);
   }
 
   unsigned long long* const sl = slabs + (uint64_t)blockIdx.x * kSlabWords;
@@ -229,16 +209,7 @@ __global__ __launch_bounds__(kClThreads) void gb_close_kernel(GbArgs a, const un
     s_first = kGbNone;
   }
   __syncthreads();
-  // this workgroup's 64 bins over the slabs: 16 slabs at a time, 512 contiguous bytes of each
-  {
-    const uint32_t grp = tid >> 6, bin = bin0 + lane;
-    uint64_t acc = 0;
-    for (uint32_t s = grp; s < nslabs; s += kClThreads / 64) {
-      const unsigned long long* const sl = slabs + (uint64_t)s * kSlabWords;
-      if (bin < sl[kSlBins]) acc += sl[kSlHist + bin];
-    }
-    if (acc) atomicAdd(&s_bins[lane], (unsigned long long)acc);
-  }
+  slab_sum_bins<kSlabWords, kSlBins, kSlHist>(slabs, nslabs, s_bins);
   __syncthreads();
   if (tid < kClBins) out[kOutHist + bin0 + tid] = s_bins[tid];
   if (blockIdx.x != 0) return;
@@ -252,7 +223,7 @@ __global__ __launch_bounds__(kClThreads) void gb_close_kernel(GbArgs a, const un
     if (have && my[kSlFirst] != kGbNone) atomicMin(&s_first, my[kSlFirst]);
   }
   uint64_t br = have ? (uint64_t)my[kSlMaxR] : kGbNone, bc = have ? (uint64_t)my[kSlMaxC] : kGbNone;
-  gb_block_best<kClThreads / 64>(br, bc, s_r, s_c);  // its barriers also order the sums above
+  block_best<kClThreads / 64>(br, bc, s_r, s_c, gb_best_better);  // its barriers also order the sums above
   if (tid == 0) {
     out[kOutGStart] = a.g_start;
     out[kOutNbits] = a.s.nbits;
@@ -268,18 +239,10 @@ __global__ __launch_bounds__(kClThreads) void gb_close_kernel(GbArgs a, const un
 }  // namespace
 
 uint32_t goldbach_grid(uint64_t nbits, int num_cus, uint32_t grid_cap) {
-  const uint64_t ntiles = mask_tiles(nbits);
-  // every workgroup walks one fixed run of tiles, so the grid is one resident round
-  uint64_t cap = grid_cap ? grid_cap : (uint64_t)kGbGridPerCu * (uint64_t)(num_cus > 0 ? num_cus : 1);
-  if (cap > kGbMaxGrid) cap = kGbMaxGrid;
-  if (ntiles <= cap) return (uint32_t)ntiles;
-  const uint64_t per = (ntiles + cap - 1) / cap;
-  return (uint32_t)((ntiles + per - 1) / per);
+  return slab_grid(nbits, kGbGridPerCu, num_cus, grid_cap, kGbMaxGrid);
 }
 
-uint64_t goldbach_scratch_bytes(uint32_t grid) {
-  return (uint64_t)(grid ? grid : 1u) * kSlabWords * sizeof(uint64_t);
-}
+uint64_t goldbach_scratch_bytes(uint32_t grid) { return slab_bytes(grid, kSlabWords); }
 
 hipError_t launch_goldbach(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint32_t mask_shift,
                            const uint64_t* below, uint32_t below_shift, uint64_t below_bits, uint32_t nprimes,
@@ -290,14 +253,8 @@ hipError_t launch_goldbach(uint64_t g_start, uint64_t nbits, const uint64_t* mas
   a.s = GbSrc{mask, below, nbits, below_bits, mask_shift, below_shift};
   a.g_start = g_start;
   a.nprimes = nprimes;
-  a.ntiles = mask_tiles(nbits);
-  if ((a.ntiles != 0) != (grid != 0)) return hipErrorInvalidValue;
-  a.tiles_per_wg = grid ? (a.ntiles + grid - 1) / grid : 0;
-  unsigned long long* const sl = reinterpret_cast<unsigned long long*>(slabs);
-  if (grid) hipLaunchKernelGGL(gb_main_kernel, dim3(grid), dim3(kGbThreads), 0, stream, a, sl);
-  hipLaunchKernelGGL(gb_close_kernel, dim3(kClGroups), dim3(kClThreads), 0, stream, a, sl, grid,
-                     reinterpret_cast<unsigned long long*>(out));
-  return hipGetLastError();
+  if (!slab_run(nbits, grid, &a.run)) return hipErrorInvalidValue;
+  return slab_launch(gb_main_kernel, gb_close_kernel, a, grid, kGbThreads, kGbPrimes, slabs, out, stream);
 }
 
 }  // namespace dse

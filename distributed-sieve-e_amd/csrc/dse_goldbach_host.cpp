@@ -37,30 +37,6 @@ int32_t gb_check_below(const uint64_t* below, uint32_t below_shift, uint64_t bel
 // whole words of a `below` of `bits` candidates that starts `shift` bits into its first word
 inline uint64_t below_words(uint32_t shift, uint64_t bits) { return (shift + bits + 63) / 64; }
 
-// Acquire the device's scratch for `stream`: the slabs of `grid` workgroups, behind them
-// `nres` results and `ncopy` copies of a neighbour's tail of `copy_words` words each.
-int32_t gb_acquire(DevState& d, uint32_t grid, uint32_t nres, uint32_t ncopy, uint64_t copy_words, hipStream_t stream,
-                   uint64_t** res, uint64_t** copies) {
-  StreamScratch& s = d.goldbach_scratch;
-  const uint64_t slabs = goldbach_scratch_bytes(grid);
-  const uint64_t need = slabs + (uint64_t)nres * sizeof(dse_goldbach) + (uint64_t)ncopy * copy_words * 8;
-  HIP_TRY(acquire_scratch_roomy(&s, need, stream));
-  char* const p = static_cast<char*>(s.buf.ptr) + slabs;
-  if (res) *res = reinterpret_cast<uint64_t*>(p);
-  if (copies) *copies = reinterpret_cast<uint64_t*>(p + (uint64_t)nres * sizeof(dse_goldbach));
-  return DSE_OK;
-}
-
-// the results at `res` to the host; drains d.stream and releases the scratch
-int32_t gb_collect(DevState& d, const uint64_t* res, uint32_t n, dse_goldbach* out) {
-  hipError_t e = hipMemcpyAsync(out, res, (uint64_t)n * sizeof(dse_goldbach), hipMemcpyDeviceToHost, d.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-  const hipError_t r = release_scratch(&d.goldbach_scratch, d.stream);
-  if (e == hipSuccess) e = r;
-  if (e != hipSuccess) return fail(DSE_EHIP, std::string("goldbach copy failed: ") + hipGetErrorString(e));
-  return DSE_OK;
-}
-
 void gb_empty(dse_goldbach* r, uint64_t g_start, uint64_t nbits, uint32_t n) {
   std::memset(r, 0, sizeof *r);
   r->g_start = g_start;
@@ -94,12 +70,10 @@ extern "C" int32_t dse_goldbach_dev_async(dse_ctx* ctx, uint64_t g_start, uint64
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t s = (hipStream_t)stream;
   const uint32_t grid = goldbach_grid(nbits, d.num_cus, ctx->goldbach_grid);
-  if ((rc = gb_acquire(d, grid, 0, 0, 0, s, nullptr, nullptr))) return rc;
-  const hipError_t e = launch_goldbach(g_start, nbits, mask_dev, 0, below_dev, below_shift, below_bits, n,
-                                       reinterpret_cast<uint64_t*>(out_dev), d.goldbach_scratch.buf.ptr, grid, s);
-  HIP_TRY(release_scratch(&d.goldbach_scratch, s));  // also after a failure: what was launched may read the scratch
-  if (e != hipSuccess) return fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
-  return DSE_OK;
+  return scratch_launch(d.goldbach_scratch, goldbach_scratch_bytes(grid), s, "goldbach launch", [&](void* slabs) {
+    return launch_goldbach(g_start, nbits, mask_dev, 0, below_dev, below_shift, below_bits, n,
+                           reinterpret_cast<uint64_t*>(out_dev), slabs, grid, s);
+  });
 }
 
 extern "C" int32_t dse_goldbach_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, uint32_t nprimes,
@@ -120,7 +94,9 @@ extern "C" int32_t dse_goldbach_range(dse_ctx* ctx, uint64_t g_start, uint64_t n
   const uint64_t* const m = d.scratch_mask.as<uint64_t>();
   const uint32_t grid = goldbach_grid(nbits, d.num_cus, ctx->goldbach_grid);
   uint64_t* res;
-  if ((rc = gb_acquire(d, grid, 1, 0, 0, d.stream, &res, nullptr))) return rc;
+  if ((rc = result_acquire(d, d.goldbach_scratch, goldbach_scratch_bytes(grid), 1, sizeof(dse_goldbach), 0, &res,
+                           nullptr)))
+    return rc;
   const hipError_t e = launch_goldbach(g_start, nbits, m + (ext >> 6), (uint32_t)(ext & 63), m, 0, ext, n, res,
                                        d.goldbach_scratch.buf.ptr, grid, d.stream);
   if (e != hipSuccess) {
@@ -128,7 +104,7 @@ extern "C" int32_t dse_goldbach_range(dse_ctx* ctx, uint64_t g_start, uint64_t n
     return fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
   }
   dse_goldbach tmp;
-  if ((rc = gb_collect(d, res, 1, &tmp))) return rc;
+  if ((rc = result_collect(d, d.goldbach_scratch, "goldbach", res, sizeof tmp, &tmp))) return rc;
   *out = tmp;
   return DSE_OK;
 }
@@ -138,12 +114,10 @@ extern "C" int32_t dse_goldbach_resident(dse_ctx* ctx, int32_t my_num, uint32_t 
   int32_t rc;
   uint32_t n;
   if ((rc = gb_nprimes(nprimes, &n))) return rc;
+  int32_t k0, k1;
+  if ((rc = resident_span(ctx, my_num, "goldbach", &k0, &k1))) return rc;
   const ResidentSet& r = ctx->resident;
-  if (!r.valid || my_num < 0 || my_num > r.P)
-    return fail(DSE_EINVAL, "chunk " + std::to_string(my_num) + " is not resident");
   const uint64_t cs = (uint64_t)r.cs;
-  const int32_t k0 = my_num ? my_num : 1, k1 = my_num ? my_num : r.P;
-  if ((rc = check_mask_range("goldbach", (uint64_t)(k1 - 1) * cs, cs))) return rc;
   // chunk k > 1 sees the last `reach` candidates of chunk k - 1
   const uint64_t reach = kGbTable.h(n - 1);
   if (k1 > 1 && cs < reach)
@@ -153,41 +127,30 @@ extern "C" int32_t dse_goldbach_resident(dse_ctx* ctx, int32_t my_num, uint32_t 
   const uint32_t tail_shift = (uint32_t)(off & 63);
   const uint64_t tail_words = k1 > 1 ? below_words(tail_shift, reach) : 0;  // through the mask's last word
 
-  // every device's launches are enqueued on its stream before any result is waited for
   const size_t nd = ctx->devs.size();
-  std::vector<std::vector<int32_t>> chunk(nd);
-  for (int32_t k = k0; k <= k1; ++k) chunk[(size_t)(k - 1) % nd].push_back(k);
-  std::vector<uint64_t*> res(nd, nullptr);
-  std::vector<bool> queued(nd, false);
-  rc = DSE_OK;
-  for (size_t i = 0; i < nd && !rc; ++i) {
-    if (chunk[i].empty()) continue;
-    DevState& d = ctx->devs[i];
-    if (hipSetDevice(d.device) != hipSuccess) {
-      rc = fail(DSE_EHIP, "hipSetDevice failed");
-      break;
-    }
-    const uint32_t cnt = (uint32_t)chunk[i].size();
+  auto enqueue = [&](DevState& d, const std::vector<int32_t>& chunks, uint64_t** res, bool* acquired) -> int32_t {
+    const uint32_t cnt = (uint32_t)chunks.size();
     const uint32_t grid = goldbach_grid(cs, d.num_cus, ctx->goldbach_grid);
     uint64_t* copies = nullptr;
-    if ((rc = gb_acquire(d, grid, cnt, nd > 1 ? cnt : 0, tail_words, d.stream, &res[i], &copies))) break;
-    queued[i] = true;
+    if (int32_t ra = result_acquire(d, d.goldbach_scratch, goldbach_scratch_bytes(grid), cnt, sizeof(dse_goldbach),
+                                    (nd > 1 ? cnt : 0) * tail_words * 8, res, &copies))
+      return ra;
+    *acquired = true;
     hipError_t e = hipSuccess;
     for (uint32_t j = 0; j < cnt && e == hipSuccess; ++j) {
-      const int32_t k = chunk[i][j];
+      const int32_t k = chunks[j];
       const uint64_t* below = nullptr;
       uint64_t below_bits = 0;
       if (k > 1 && reach) {
-        const size_t src = (size_t)(k - 2) % nd;
+        const DevState& sd = ctx->devs[(size_t)(k - 2) % nd];
         const uint64_t* const tail = r.masks[k - 2].as<uint64_t>() + (off >> 6);
         below_bits = reach;
-        if (src == i) {
+        if (&sd == &d) {
           below = tail;  // the neighbour's mask is this device's: a pointer into it
         } else {
           // the neighbour's whole words into this device's scratch, on this device's stream: the
           // launch behind it is ordered by the stream, the scratch's next user by its event
           uint64_t* const dst = copies + (uint64_t)j * tail_words;
-          const DevState& sd = ctx->devs[src];
           e = sd.device == d.device
                   ? hipMemcpyAsync(dst, tail, tail_words * 8, hipMemcpyDeviceToDevice, d.stream)
                   : hipMemcpyPeerAsync(dst, d.device, tail, sd.device, tail_words * 8, d.stream);
@@ -196,28 +159,13 @@ extern "C" int32_t dse_goldbach_resident(dse_ctx* ctx, int32_t my_num, uint32_t 
       }
       if (e == hipSuccess)
         e = launch_goldbach((uint64_t)(k - 1) * cs, cs, r.masks[k - 1].as<uint64_t>(), 0, below, tail_shift, below_bits,
-                            n, res[i] + (uint64_t)j * DSE_GOLDBACH_WORDS, d.goldbach_scratch.buf.ptr, grid, d.stream);
+                            n, *res + (uint64_t)j * DSE_GOLDBACH_WORDS, d.goldbach_scratch.buf.ptr, grid, d.stream);
     }
-    if (e != hipSuccess) rc = fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
-  }
-  std::vector<dse_goldbach> parts((size_t)(k1 - k0 + 1));
-  std::vector<dse_goldbach> got;
-  for (size_t i = 0; i < nd; ++i) {  // collect what was enqueued, also after a failure: the scratch must be released
-    if (!queued[i]) continue;
-    DevState& d = ctx->devs[i];
-    (void)hipSetDevice(d.device);
-    got.resize(chunk[i].size());
-    const int32_t r2 = gb_collect(d, res[i], (uint32_t)chunk[i].size(), got.data());
-    if (r2 && !rc) rc = r2;
-    if (!r2)
-      for (size_t j = 0; j < got.size(); ++j) parts[(size_t)(chunk[i][j] - k0)] = got[j];
-  }
-  if (rc) return rc;
-  dse_goldbach acc = parts[0];
-  for (size_t j = 1; j < parts.size(); ++j)
-    if ((rc = dse_goldbach_merge(&acc, &parts[j], &acc))) return rc;
-  *out = acc;
-  return DSE_OK;
+    if (e != hipSuccess) return fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
+    return DSE_OK;
+  };
+  return resident_reduce<dse_goldbach>(ctx, k0, k1, &DevState::goldbach_scratch, "goldbach", enqueue,
+                                       dse_goldbach_merge, out);
 }
 
 extern "C" int32_t dse_goldbach_merge(const dse_goldbach* a, const dse_goldbach* b, dse_goldbach* out) {

@@ -1,9 +1,10 @@
 // dse_host.cpp -- C-ABI host layer of libdse.so (include/dse.h): contexts,
 // chunk geometry, the base table and its sharing, collectives, the sieve entry
 // points, debug options and stats, and what the other host units share (range
-// checks, scratch growth, the two-slot slab pipe). The finish side is
+// and residency checks, scratch growth, the result scratch and per-device fan-out
+// of resident chunks, the two-slot slab pipe). The finish side is
 // dse_finish_host.cpp, primes as numbers dse_primes_host.cpp, statistics
-// dse_stats_host.cpp, rank and select dse_query_host.cpp.
+// dse_stats_host.cpp, rank and select dse_query_host.cpp, Goldbach dse_goldbach_host.cpp.
 //
 // Replaces the reference's orchestration of the hot path:
 //   spread-work (sieve.clj:15-34)            -> dse_spread_work (exact int64)
@@ -104,13 +105,72 @@ int32_t check_mask_range(const char* what, uint64_t g_start, uint64_t nbits) {
   return DSE_OK;
 }
 
-int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mask) {
+int32_t check_resident(dse_ctx* ctx, int32_t my_num, bool one_chunk) {
   const ResidentSet& r = ctx->resident;
-  if (!r.valid || my_num < 1 || my_num > r.P)
+  if (!r.valid || my_num < 0 || my_num > r.P || (one_chunk && !my_num))
     return fail(DSE_EINVAL, "chunk " + std::to_string(my_num) + " is not resident");
-  *d = &ctx->devs[(size_t)(my_num - 1) % ctx->devs.size()];
-  *mask = r.masks[my_num - 1].as<uint64_t>();
   return DSE_OK;
+}
+
+int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mask) {
+  if (int32_t rc = check_resident(ctx, my_num, true)) return rc;
+  *d = &ctx->devs[(size_t)(my_num - 1) % ctx->devs.size()];
+  *mask = ctx->resident.masks[my_num - 1].as<uint64_t>();
+  return DSE_OK;
+}
+
+int32_t resident_span(dse_ctx* ctx, int32_t my_num, const char* what, int32_t* k0, int32_t* k1) {
+  if (int32_t rc = check_resident(ctx, my_num, false)) return rc;
+  const ResidentSet& r = ctx->resident;
+  *k0 = my_num ? my_num : 1;
+  *k1 = my_num ? my_num : r.P;
+  return check_mask_range(what, (uint64_t)(*k1 - 1) * (uint64_t)r.cs, (uint64_t)r.cs);
+}
+
+int32_t result_acquire(DevState& d, StreamScratch& s, uint64_t slab_bytes, uint32_t nres, uint64_t res_bytes,
+                       uint64_t extra_bytes, uint64_t** res, uint64_t** extra) {
+  HIP_TRY(acquire_scratch_roomy(&s, slab_bytes + nres * res_bytes + extra_bytes, d.stream));
+  char* const p = static_cast<char*>(s.buf.ptr) + slab_bytes;
+  *res = reinterpret_cast<uint64_t*>(p);
+  if (extra) *extra = reinterpret_cast<uint64_t*>(p + nres * res_bytes);
+  return DSE_OK;
+}
+
+int32_t result_collect(DevState& d, StreamScratch& s, const char* what, const uint64_t* res, uint64_t n, void* out) {
+  hipError_t e = hipMemcpyAsync(out, res, n, hipMemcpyDeviceToHost, d.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+  const hipError_t r = release_scratch(&s, d.stream);
+  if (e == hipSuccess) e = r;
+  if (e != hipSuccess) return fail(DSE_EHIP, std::string(what) + " copy failed: " + hipGetErrorString(e));
+  return DSE_OK;
+}
+
+int32_t resident_fanout(dse_ctx* ctx, int32_t k0, int32_t k1, const FanEnqueue& enqueue, const FanCollect& collect) {
+  const size_t nd = ctx->devs.size();
+  std::vector<std::vector<int32_t>> chunks(nd);
+  for (int32_t k = k0; k <= k1; ++k) chunks[(size_t)(k - 1) % nd].push_back(k);
+  // every device's launches are enqueued on its stream before any result is waited for
+  std::vector<char> acquired(nd, 0);
+  int32_t rc = DSE_OK;
+  for (size_t i = 0; i < nd && !rc; ++i) {
+    if (chunks[i].empty()) continue;
+    DevState& d = ctx->devs[i];
+    bool a = false;
+    rc = hipSetDevice(d.device) == hipSuccess ? enqueue(i, d, chunks[i], &a) : fail(DSE_EHIP, "hipSetDevice failed");
+    acquired[i] = a;
+  }
+  std::string msg = rc ? g_err : std::string();
+  for (size_t i = 0; i < nd; ++i) {  // collect what was enqueued, also after a failure: the scratch must be released
+    if (!acquired[i]) continue;
+    DevState& d = ctx->devs[i];
+    (void)hipSetDevice(d.device);
+    const int32_t r = collect(i, d, chunks[i]);
+    if (r && !rc) {
+      rc = r;
+      msg = g_err;
+    }
+  }
+  return rc ? fail(rc, msg) : DSE_OK;  // the first failure, whatever a collect behind it said
 }
 
 int32_t ensure_slab_pipe(DevState& d, uint64_t want) {

@@ -2,10 +2,12 @@
 // contexts, tables, collectives, sieve entry points; dse_finish_host.cpp: the
 // primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
 // dse_stats_host.cpp: statistics of a mask; dse_query_host.cpp: rank and
-// select; dse_goldbach_host.cpp: minimal Goldbach partitions). Not installed; include/dse.h is the ABI.
+// select; dse_goldbach_host.cpp: minimal Goldbach partitions): contexts, device state, the slab
+// pipe, and the result pass over resident chunks. Not installed; include/dse.h is the ABI.
 #pragma once
 #include <rccl/rccl.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -131,8 +133,66 @@ int32_t check_mask_range(const char* what, uint64_t g_start, uint64_t nbits);
 // keep_dev: sieve into d.scratch_mask even without a host mask (dse_finish_range_file)
 int32_t sieve_range_host(dse_ctx* ctx, DevState& d, uint64_t g0, uint64_t nbits, uint64_t* mask_or_null,
                          uint64_t* count, bool keep_dev = false);
-// The device and mask of resident chunk my_num; DSE_EINVAL when it is not resident.
+// DSE_EINVAL, naming my_num, unless it is a resident chunk or, without one_chunk, 0 for all of them.
+int32_t check_resident(dse_ctx* ctx, int32_t my_num, bool one_chunk);
+// The device and mask of resident chunk my_num (check_resident for one chunk).
 int32_t find_resident(dse_ctx* ctx, int32_t my_num, DevState** d, uint64_t** mask);
+// check_resident, my_num's chunks k0 .. k1 (itself, or all for 0), check_mask_range(what) of the last.
+int32_t resident_span(dse_ctx* ctx, int32_t my_num, const char* what, int32_t* k0, int32_t* k1);
+
+// A *_dev_async entry point's launches around a scratch: acquire `s` for `stream`, launch(its
+// address), release also after a failure (what was launched may read it); "<what> failed: ...".
+template <typename Launch>
+int32_t scratch_launch(StreamScratch& s, uint64_t bytes, hipStream_t stream, const char* what, Launch&& launch) {
+  HIP_TRY(acquire_scratch_roomy(&s, bytes, stream));
+  const hipError_t e = launch(s.buf.ptr);
+  HIP_TRY(release_scratch(&s, stream));
+  if (e != hipSuccess) return fail(DSE_EHIP, std::string(what) + " failed: " + hipGetErrorString(e));
+  return DSE_OK;
+}
+
+// Results on their way to the host through a scratch laid out as slabs (dse_slab.h) | nres results
+// of res_bytes | extra_bytes of the unit's own: result_acquire acquires it for d.stream and gives
+// the two addresses behind the slabs; result_collect copies n bytes from res to `out` on d.stream,
+// drains the stream and releases, also after an error ("<what> copy failed: ...").
+int32_t result_acquire(DevState& d, StreamScratch& s, uint64_t slab_bytes, uint32_t nres, uint64_t res_bytes,
+                       uint64_t extra_bytes, uint64_t** res, uint64_t** extra);
+int32_t result_collect(DevState& d, StreamScratch& s, const char* what, const uint64_t* res, uint64_t n, void* out);
+
+// The per-device fan-out over the resident chunks k0 .. k1. For every device that holds some:
+// hipSetDevice and enqueue(device index, DevState, its chunks, &acquired), which acquires a scratch
+// (and says so) and launches on d.stream without waiting. Then for every device that acquired,
+// also after a failure: hipSetDevice and collect(...), which waits and releases. The first error.
+using FanEnqueue = std::function<int32_t(size_t, DevState&, const std::vector<int32_t>&, bool*)>;
+using FanCollect = std::function<int32_t(size_t, DevState&, const std::vector<int32_t>&)>;
+int32_t resident_fanout(dse_ctx* ctx, int32_t k0, int32_t k1, const FanEnqueue& enqueue, const FanCollect& collect);
+
+// One result R per chunk k0 .. k1, folded into *out in chunk order by the unit's merge. enqueue(
+// DevState&, its chunks, &res, &acquired) result_acquires d.*scratch with one R per chunk at *res.
+template <typename R, typename Enqueue>
+int32_t resident_reduce(dse_ctx* ctx, int32_t k0, int32_t k1, StreamScratch DevState::*scratch, const char* what,
+                        Enqueue&& enqueue, int32_t (*merge)(const R*, const R*, R*), R* out) {
+  std::vector<R> parts((size_t)(k1 - k0 + 1)), got;
+  std::vector<uint64_t*> res(ctx->devs.size(), nullptr);
+  int32_t rc = resident_fanout(
+      ctx, k0, k1,
+      [&](size_t i, DevState& d, const std::vector<int32_t>& chunks, bool* acquired) {
+        return enqueue(d, chunks, &res[i], acquired);
+      },
+      [&](size_t i, DevState& d, const std::vector<int32_t>& chunks) {
+        got.resize(chunks.size());
+        const int32_t r = result_collect(d, d.*scratch, what, res[i], chunks.size() * sizeof(R), got.data());
+        if (!r)
+          for (size_t j = 0; j < got.size(); ++j) parts[(size_t)(chunks[j] - k0)] = got[j];
+        return r;
+      });
+  if (rc) return rc;
+  R acc = parts[0];
+  for (size_t j = 1; j < parts.size(); ++j)
+    if ((rc = merge(&acc, &parts[j], &acc))) return rc;
+  *out = acc;
+  return DSE_OK;
+}
 // The slab pipe (d.pipe; dse_host.cpp), the device current. ensure_slab_pipe: its stream, events,
 // totals and four buffers of min(max(want, 1 MiB), 64 MiB) bytes each, no slot pending.
 int32_t ensure_slab_pipe(DevState& d, uint64_t want);

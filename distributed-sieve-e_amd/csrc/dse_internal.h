@@ -5,7 +5,8 @@
 // dse_goldbach_host.cpp). Not installed;
 // include/dse.h is the ABI. The units that read a resident mask (finish,
 // primes, stats, query, goldbach) share its range, tiles and clipped word load (dse_mask.h);
-// every unit with a workgroup sum or scan takes it from dse_block.h.
+// every unit with a workgroup sum, scan or best-of takes it from dse_block.h; the two that reduce
+// a range to one struct through per-workgroup slabs (stats, goldbach) share dse_slab.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -237,12 +238,10 @@ hipError_t launch_primes_emit(uint64_t g_start, uint64_t nbits, const uint64_t* 
                               uint64_t out_cap, const void* tile_sums, uint64_t tile0, uint64_t tiles,
                               hipStream_t stream);
 
-// Statistics of a mask (dse_stats.hip): the main launch over `grid` workgroups,
-// each walking its own run of tiles of kMaskTileBits candidates, and the
-// closing launch, which writes the dse_stats (kStatsWords uint64 words) at
-// `stats`. grid = stats_grid(nbits, CUs of the device, cap or 0): 0 exactly for
-// an empty range, at most kStatsMaxGrid. slabs: stats_scratch_bytes(grid) bytes
-// of device scratch. patterns: npatterns <= 8 host values, passed by value.
+// Statistics of a mask (dse_stats.hip): the two launches of a slab reduction (dse_slab.h), which
+// write the dse_stats (kStatsWords uint64 words) at `stats`. grid = stats_grid(nbits, CUs of the
+// device, cap or 0): slab_grid's rule. slabs: stats_scratch_bytes(grid) bytes of device scratch.
+// patterns: npatterns <= 8 host values, passed by value.
 constexpr uint32_t kStatsMaxGrid = 1024;
 constexpr uint32_t kStatsWords = 27 + 1024;
 uint32_t stats_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
@@ -265,14 +264,12 @@ uint32_t query_grid(uint32_t kind, uint64_t nq, int num_cus, uint32_t grid_cap);
 hipError_t launch_query(uint32_t kind, uint64_t g_start, uint64_t nbits, const uint64_t* mask, const void* index,
                         const uint64_t* q, uint64_t nq, uint64_t* out, uint32_t grid, hipStream_t stream);
 
-// Minimal Goldbach partitions of a mask (dse_goldbach.hip): the main launch over `grid`
-// workgroups, each walking its own run of tiles of kMaskTileBits candidates, and the closing
-// launch, which writes the dse_goldbach (kGbWords uint64 words) at `out`. The range's candidates
+// Minimal Goldbach partitions of a mask (dse_goldbach.hip): the two launches of a slab reduction
+// (dse_slab.h), which write the dse_goldbach (kGbWords uint64 words) at `out`. The range's candidates
 // are the bits of `mask` from bit mask_shift on (0 for a caller's mask; dse_goldbach_range's lies
 // behind its `below` in one scratch mask), the below_bits candidates below it the bits of `below`
 // from bit below_shift on; nprimes in 1..2048. grid = goldbach_grid(nbits, CUs of the device, cap
-// or 0): 0 exactly for an empty range, at most kGbMaxGrid. slabs:
-// goldbach_scratch_bytes(grid) bytes of device scratch.
+// or 0): slab_grid's rule. slabs: goldbach_scratch_bytes(grid) bytes of device scratch.
 constexpr uint32_t kGbMaxGrid = 1024;
 constexpr uint32_t kGbWords = 8 + 2048;
 uint32_t goldbach_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);

@@ -1,7 +1,8 @@
 // dse_mask.h -- a range of a prime mask and its words, shared by everything
 // that turns a device-resident mask into something else: the device finish
 // (dse_finish.hip), primes as numbers (dse_primes.hip), the statistics
-// (dse_stats.hip) and their host sides.
+// (dse_stats.hip), rank and select (dse_query.hip), the Goldbach partitions
+// (dse_goldbach.hip) and their host sides.
 //
 // A range is the odd indices [g_start, g_start + nbits), one bit each, in
 // `words` 64-bit words; the kernels walk it in tiles of kMaskTileWords words,

@@ -13,12 +13,6 @@ using namespace dse;
 
 namespace {
 
-// The tile-sum scratch of the device, ordered against whatever stream used it last.
-int32_t primes_acquire(DevState& d, uint64_t nbits, hipStream_t stream) {
-  HIP_TRY(acquire_scratch_roomy(&d.primes_sums, primes_scratch_bytes(nbits), stream));
-  return DSE_OK;
-}
-
 // The slab pipeline: mask_dev (ready in d.stream's order) -> out. The size and
 // scan launches run once; the scanned tile sums are copied to the host, and
 // every slab of at most `slab` ranks is emitted over the tiles that hold its
@@ -40,7 +34,7 @@ int32_t primes_pipeline(dse_ctx* ctx, DevState& d, uint64_t g_start, uint64_t nb
 
   auto run = [&]() -> int32_t {
     int32_t r;
-    if ((r = primes_acquire(d, nbits, d.stream))) return r;
+    HIP_TRY(acquire_scratch_roomy(&d.primes_sums, primes_scratch_bytes(nbits), d.stream));
     acquired = true;
     void* const sums = d.primes_sums.buf.ptr;
     HIP_TRY(launch_primes_scan(g_start, nbits, mask_dev, first, out_cap, f.dtotals, sums, d.stream));
@@ -110,15 +104,13 @@ extern "C" int32_t dse_primes_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t
   DevState& d = ctx->devs[0];
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = primes_acquire(d, nbits, s))) return rc;
-  void* const sums = d.primes_sums.buf.ptr;
-  hipError_t e = launch_primes_scan(g_start, nbits, mask_dev, first, out_cap,
-                                    reinterpret_cast<unsigned long long*>(totals_dev), sums, s);
-  if (e == hipSuccess)
-    e = launch_primes_emit(g_start, nbits, mask_dev, first, out_dev, out_cap, sums, 0, mask_tiles(nbits), s);
-  HIP_TRY(release_scratch(&d.primes_sums, s));  // also after a failure: what was launched may read the scratch
-  if (e != hipSuccess) return fail(DSE_EHIP, std::string("primes launch failed: ") + hipGetErrorString(e));
-  return DSE_OK;
+  return scratch_launch(d.primes_sums, primes_scratch_bytes(nbits), s, "primes launch", [&](void* sums) {
+    hipError_t e = launch_primes_scan(g_start, nbits, mask_dev, first, out_cap,
+                                      reinterpret_cast<unsigned long long*>(totals_dev), sums, s);
+    if (e == hipSuccess)
+      e = launch_primes_emit(g_start, nbits, mask_dev, first, out_dev, out_cap, sums, 0, mask_tiles(nbits), s);
+    return e;
+  });
 }
 
 extern "C" int32_t dse_primes_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, uint64_t first, uint64_t* out,

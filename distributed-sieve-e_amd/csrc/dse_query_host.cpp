@@ -127,50 +127,41 @@ int32_t ensure_indices(dse_ctx* ctx, int32_t k0, int32_t k1) {
   return rc;
 }
 
-// The batches of the resident chunks, each on its chunk's device and stream: every device's
-// batches are enqueued before any is waited for. Returns with every stream drained.
-int32_t run_batches(dse_ctx* ctx, uint32_t kind, const std::vector<Batch>& batches) {
+// The batches of the resident chunks k0 .. k1, each on its chunk's device and stream (resident_fanout).
+// Returns with every stream drained, also after a failure: what was enqueued reads the caller's memory.
+int32_t run_batches(dse_ctx* ctx, uint32_t kind, int32_t k0, int32_t k1, const std::vector<Batch>& batches) {
   const ResidentSet& r = ctx->resident;
   const uint64_t cs = (uint64_t)r.cs;
   const size_t nd = ctx->devs.size();
-  std::vector<bool> acquired(nd, false);
-  int32_t rc = DSE_OK;
-  for (size_t i = 0; i < nd && !rc; ++i) {
-    uint64_t bytes = 0;
-    for (const Batch& b : batches)
-      if ((size_t)(b.chunk - 1) % nd == i) bytes += 16 * b.n;
-    if (!bytes) continue;
-    DevState& d = ctx->devs[i];
-    hipError_t e = hipSetDevice(d.device);
-    if (e != hipSuccess) {
-      rc = fail(DSE_EHIP, "hipSetDevice failed");
-      break;
-    }
-    if ((rc = hip_or_nomem(acquire_scratch_roomy(&d.query_scratch, bytes, d.stream), "hipMalloc of the query buffers")))
-      break;
-    acquired[i] = true;
-    char* dev = d.query_scratch.buf.as<char>();
-    for (const Batch& b : batches) {
-      if ((size_t)(b.chunk - 1) % nd != i || !b.n) continue;
-      const size_t c = (size_t)b.chunk - 1;
-      e = enqueue_batch(ctx, d, kind, (uint64_t)c * cs, cs, r.masks[c].as<uint64_t>(), r.index[c].ptr, b, dev, d.stream);
-      if (e != hipSuccess) {
-        rc = fail(DSE_EHIP, std::string("query launch failed: ") + hipGetErrorString(e));
-        break;
-      }
-      dev += 16 * b.n;
-    }
-  }
-  for (size_t i = 0; i < nd; ++i) {  // also after a failure: what was enqueued reads the caller's memory
-    if (!acquired[i]) continue;
-    DevState& d = ctx->devs[i];
-    (void)hipSetDevice(d.device);
-    hipError_t e = hipStreamSynchronize(d.stream);
-    const hipError_t e2 = release_scratch(&d.query_scratch, d.stream);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess && !rc) rc = fail(DSE_EHIP, std::string("query copy failed: ") + hipGetErrorString(e));
-  }
-  return rc;
+  return resident_fanout(
+      ctx, k0, k1,
+      [&](size_t i, DevState& d, const std::vector<int32_t>&, bool* acquired) -> int32_t {
+        uint64_t bytes = 0;
+        for (const Batch& b : batches)
+          if ((size_t)(b.chunk - 1) % nd == i) bytes += 16 * b.n;
+        if (!bytes) return DSE_OK;
+        if (int32_t rc = hip_or_nomem(acquire_scratch_roomy(&d.query_scratch, bytes, d.stream),
+                                      "hipMalloc of the query buffers"))
+          return rc;
+        *acquired = true;
+        char* dev = d.query_scratch.buf.as<char>();
+        for (const Batch& b : batches) {
+          if ((size_t)(b.chunk - 1) % nd != i || !b.n) continue;
+          const size_t c = (size_t)b.chunk - 1;
+          const uint64_t* const mask = r.masks[c].as<uint64_t>();
+          const hipError_t e = enqueue_batch(ctx, d, kind, (uint64_t)c * cs, cs, mask, r.index[c].ptr, b, dev, d.stream);
+          if (e != hipSuccess) return fail(DSE_EHIP, std::string("query launch failed: ") + hipGetErrorString(e));
+          dev += 16 * b.n;
+        }
+        return DSE_OK;
+      },
+      [](size_t, DevState& d, const std::vector<int32_t>&) -> int32_t {
+        hipError_t e = hipStreamSynchronize(d.stream);
+        const hipError_t e2 = release_scratch(&d.query_scratch, d.stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return fail(DSE_EHIP, std::string("query copy failed: ") + hipGetErrorString(e));
+        return DSE_OK;
+      });
 }
 
 }  // namespace
@@ -245,14 +236,14 @@ extern "C" int32_t dse_query_resident(dse_ctx* ctx, int32_t my_num, uint32_t kin
   if (!ctx) return fail(DSE_EINVAL, "null ctx");
   int32_t rc;
   if ((rc = query_check("dse_query_resident", kind, q, nq, out))) return rc;
-  ResidentSet& r = ctx->resident;
-  if (!r.valid || my_num < 0 || my_num > r.P)
-    return fail(DSE_EINVAL, "chunk " + std::to_string(my_num) + " is not resident");
+  // the two halves of resident_span, the batch's bound between them: which error wins stays as it was
+  if ((rc = check_resident(ctx, my_num, false))) return rc;
   if (nq > kQueryMaxBatch) return fail(DSE_ENOMEM, "more than 2^40 queries in one call");
+  ResidentSet& r = ctx->resident;
   const uint64_t cs = (uint64_t)r.cs, P = (uint64_t)r.P;
   if (my_num == 0 && P == 1) my_num = 1;  // one chunk is the whole range
-  const int32_t k0 = my_num ? my_num : 1, k1 = my_num ? my_num : r.P;
-  if ((rc = check_mask_range("query", (uint64_t)(k1 - 1) * cs, cs))) return rc;
+  int32_t k0, k1;
+  if ((rc = resident_span(ctx, my_num, "query", &k0, &k1))) return rc;
   if (!nq) return DSE_OK;
   if (kind != kQueryTest && (rc = ensure_indices(ctx, k0, k1))) return rc;
 
@@ -262,7 +253,7 @@ extern "C" int32_t dse_query_resident(dse_ctx* ctx, int32_t my_num, uint32_t kin
     b.q = q;
     b.a = out;
     b.n = nq;
-    return run_batches(ctx, kind, {b});
+    return run_batches(ctx, kind, k0, k1, {b});
   }
 
   // All chunks as one range: every query goes to the chunk that holds its candidate (its rank,
@@ -307,7 +298,7 @@ extern "C" int32_t dse_query_resident(dse_ctx* ctx, int32_t my_num, uint32_t kin
     b.n = cq[j].size();
     batches.push_back(b);
   }
-  if ((rc = run_batches(ctx, kind, batches))) return rc;
+  if ((rc = run_batches(ctx, kind, k0, k1, batches))) return rc;
   for (uint64_t j = 0; j < P; ++j) {
     // what a NEXT or PREV that finds nothing in chunk j + 1 takes from the non-empty chunk after or before it
     uint64_t hop = kQueryNone;

@@ -29,8 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dse_block.h"
 #include "dse_internal.h"
+#include "dse_slab.h"
 #include "dse_stats_word.h"
 
 namespace dse {
@@ -45,8 +45,7 @@ constexpr uint32_t kStFlushTiles = 1u << 20;
 // a workgroup's slab, in uint64 words
 constexpr uint32_t kSlPrimes = 0, kSlFirst = 1, kSlLast1 = 2, kSlMaxD = 3, kSlMaxI = 4, kSlOverflow = 5, kSlBins = 6,
                    kSlMatches = 8, kSlHist = 16, kSlabWords = kSlHist + kStatsBins;
-// the closing kernel: one thread per slab, 64 bins per workgroup
-constexpr uint32_t kClThreads = 1024, kClBins = 64, kClGroups = kStatsBins / kClBins;
+constexpr uint32_t kClThreads = kSlabCloseThreads, kClBins = kSlabCloseBins;
 static_assert(kStatsMaxGrid <= kClThreads, "the closing kernel scans one slab per thread");
 
 // dse_stats as uint64 words
@@ -57,7 +56,7 @@ static_assert(kOutGaps + kStatsBins == kStatsWords, "dse_stats is kStatsWords wo
 
 struct StArgs {
   MaskRange r;
-  uint64_t ntiles, tiles_per_wg;
+  SlabRun run;
   uint64_t last_mask;  // the bits of the last word that lie inside the range
   uint32_t npat;
   uint32_t pat[8];
@@ -68,38 +67,6 @@ struct StArgs {
 // their use, and the clipping works on what they brought with a precomputed last_mask.
 __device__ __forceinline__ uint64_t st_fix(const StArgs& a, uint64_t wi, uint64_t v) {
   return wi < a.r.words ? v & (wi == a.r.words - 1 ? a.last_mask : ~0ull) : 0ull;
-}
-
-// the wave's best (longest, then lowest) maximal-gap candidate, in every lane
-__device__ __forceinline__ void st_wave_best(uint64_t& bd, uint64_t& bi) {
-  for (uint32_t o = 32; o > 0; o >>= 1) {
-    const uint64_t od = (uint64_t)__shfl_xor((unsigned long long)bd, o);
-    const uint64_t oi = (uint64_t)__shfl_xor((unsigned long long)bi, o);
-    if (stats_better(od, oi, bd, bi)) {
-      bd = od;
-      bi = oi;
-    }
-  }
-}
-
-// the workgroup's best candidate, in every thread (two barriers)
-template <uint32_t kWaves>
-__device__ __forceinline__ void st_block_best(uint64_t& bd, uint64_t& bi, unsigned long long* s_bd,
-                                              unsigned long long* s_bi) {
-  st_wave_best(bd, bi);
-  __syncthreads();  // the arrays' last readers
-  if ((threadIdx.x & 63u) == 0) {
-    s_bd[threadIdx.x >> 6] = bd;
-    s_bi[threadIdx.x >> 6] = bi;
-  }
-  __syncthreads();
-  bd = s_bd[0];
-  bi = s_bi[0];
-  for (uint32_t i = 1; i < kWaves; ++i)
-    if (stats_better(s_bd[i], s_bi[i], bd, bi)) {
-      bd = s_bd[i];
-      bi = s_bi[i];
-    }
 }
 
 __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, unsigned long long* __restrict__ slabs) {
@@ -149,8 +116,8 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
     pc = 0;
   };
 
-  const uint64_t t0 = (uint64_t)blockIdx.x * a.tiles_per_wg;
-  const uint64_t t1 = min(a.ntiles, t0 + a.tiles_per_wg);
+  uint64_t t0, t1;
+  slab_tiles(a.run, t0, t1);
   // This thread's word of each of the tiles t .. t + kStDepth - 1 and the low half of the word
   // after it, as they lie in memory: plain loads at clamped addresses with no use behind them, so
   // all of them stay in flight; tile() drops what lies outside the range (st_fix).
@@ -225,7 +192,7 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
     }
   }
   flush();
-  st_block_best<kStWaves>(bd, bi, s_bd, s_bi);
+  block_best<kStWaves>(bd, bi, s_bd, s_bi, stats_better);
 
   if (bd == 0 && carry != 0) {
     // no gap of more than kStatsSmall places in the whole run (synthetic masks, tiny
@@ -235,7 +202,7 @@ __global__ __launch_bounds__(kStThreads, 3) void stats_main_kernel(StArgs a, uns
       const uint64_t wi = t * kMaskTileWords + tid;
       stats_small_best(mask_word(a.r, wi), (uint32_t)mask_word(a.r, wi + 1), wi * 64ull, bd, bi);
     }
-    st_block_best<kStWaves>(bd, bi, s_bd, s_bi);
+    block_best<kStWaves>(bd, bi, s_bd, s_bi, stats_better);
   }
 
   // the slab: the barriers above made every LDS sum final
@@ -298,16 +265,7 @@ __global__ __launch_bounds__(kClThreads) void stats_close_kernel(StArgs a, const
     }
   }
 
-  // this workgroup's 64 bins over the slabs: 16 slabs at a time, 512 contiguous bytes of each
-  {
-    const uint32_t grp = tid >> 6, bin = bin0 + lane;
-    uint64_t acc = 0;
-    for (uint32_t s = grp; s < nslabs; s += kClThreads / 64) {
-      const unsigned long long* const sl = slabs + (uint64_t)s * kSlabWords;
-      if (bin < sl[kSlBins]) acc += sl[kSlHist + bin];
-    }
-    if (acc) atomicAdd(&s_bins[lane], (unsigned long long)acc);
-  }
+  slab_sum_bins<kSlabWords, kSlBins, kSlHist>(slabs, nslabs, s_bins);
   __syncthreads();
   if (tid < kClBins) out[kOutGaps + bin0 + tid] = s_bins[tid];
   if (!lead) return;
@@ -324,7 +282,7 @@ __global__ __launch_bounds__(kClThreads) void stats_close_kernel(StArgs a, const
     bd = my[kSlMaxD];
     bi = my[kSlMaxI];
   }
-  st_block_best<kClThreads / 64>(bd, bi, s_bd, s_bi);  // its barriers also order the sums above
+  block_best<kClThreads / 64>(bd, bi, s_bd, s_bi, stats_better);  // its barriers also order the sums above
   if (tid == 0) {
     out[kOutGStart] = a.r.g_start;
     out[kOutNbits] = a.r.nbits;
@@ -350,17 +308,10 @@ __global__ __launch_bounds__(kClThreads) void stats_close_kernel(StArgs a, const
 }  // namespace
 
 uint32_t stats_grid(uint64_t nbits, int num_cus, uint32_t grid_cap) {
-  const uint64_t ntiles = mask_tiles(nbits);
-  // every workgroup walks one fixed run of tiles, so the grid is one resident round: the main
-  // kernel's registers admit 3 workgroups per compute unit (make resources), a fourth would queue
-  uint64_t cap = grid_cap ? grid_cap : 3ull * (uint64_t)(num_cus > 0 ? num_cus : 1);
-  if (cap > kStatsMaxGrid) cap = kStatsMaxGrid;
-  if (ntiles <= cap) return (uint32_t)ntiles;
-  const uint64_t per = (ntiles + cap - 1) / cap;
-  return (uint32_t)((ntiles + per - 1) / per);
+  return slab_grid(nbits, 3, num_cus, grid_cap, kStatsMaxGrid);  // stats_main_kernel's registers admit 3 per CU
 }
 
-uint64_t stats_scratch_bytes(uint32_t grid) { return (uint64_t)(grid ? grid : 1u) * kSlabWords * sizeof(uint64_t); }
+uint64_t stats_scratch_bytes(uint32_t grid) { return slab_bytes(grid, kSlabWords); }
 
 hipError_t launch_stats(uint64_t g_start, uint64_t nbits, const uint64_t* mask, const uint32_t* patterns,
                         uint32_t npatterns, uint64_t* stats, void* slabs, uint32_t grid, hipStream_t stream) {
@@ -368,16 +319,10 @@ hipError_t launch_stats(uint64_t g_start, uint64_t nbits, const uint64_t* mask, 
   StArgs a;
   a.r = mask_range(mask, g_start, nbits);
   a.last_mask = (nbits & 63) ? (1ull << (nbits & 63)) - 1 : ~0ull;
-  a.ntiles = mask_tiles(nbits);
-  if ((a.ntiles != 0) != (grid != 0)) return hipErrorInvalidValue;
-  a.tiles_per_wg = grid ? (a.ntiles + grid - 1) / grid : 0;
+  if (!slab_run(nbits, grid, &a.run)) return hipErrorInvalidValue;
   a.npat = npatterns;
   for (uint32_t p = 0; p < 8; ++p) a.pat[p] = p < npatterns ? patterns[p] : 0u;
-  unsigned long long* const sl = reinterpret_cast<unsigned long long*>(slabs);
-  if (grid) hipLaunchKernelGGL(stats_main_kernel, dim3(grid), dim3(kStThreads), 0, stream, a, sl);
-  hipLaunchKernelGGL(stats_close_kernel, dim3(kClGroups), dim3(kClThreads), 0, stream, a, sl, grid,
-                     reinterpret_cast<unsigned long long*>(stats));
-  return hipGetLastError();
+  return slab_launch(stats_main_kernel, stats_close_kernel, a, grid, kStThreads, kStatsBins, slabs, stats, stream);
 }
 
 }  // namespace dse

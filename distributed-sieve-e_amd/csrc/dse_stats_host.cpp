@@ -25,46 +25,6 @@ int32_t stats_check_patterns(const uint32_t* patterns, uint32_t npatterns) {
   return DSE_OK;
 }
 
-// Acquire the device's slab scratch for `stream` with room for `nres` results
-// behind the slabs of `grid` workgroups; *res = the first result's device address.
-int32_t stats_acquire(DevState& d, uint32_t grid, uint32_t nres, hipStream_t stream, uint64_t** res) {
-  StreamScratch& s = d.stats_scratch;
-  const uint64_t slabs = stats_scratch_bytes(grid);
-  const uint64_t need = slabs + (uint64_t)nres * sizeof(dse_stats);
-  HIP_TRY(acquire_scratch_roomy(&s, need, stream));
-  if (res) *res = reinterpret_cast<uint64_t*>(static_cast<char*>(s.buf.ptr) + slabs);
-  return DSE_OK;
-}
-
-// The statistics of `n` ranges (g[i], nbits, masks[i]) of one device, launched one
-// after another on d.stream into the scratch's result slots: nothing is waited for.
-// The caller releases the scratch once it has copied the results out.
-int32_t stats_enqueue(dse_ctx* ctx, DevState& d, const uint64_t* g, uint64_t nbits, uint64_t* const* masks, uint32_t n,
-                      const uint32_t* patterns, uint32_t npatterns, uint64_t** res) {
-  const uint32_t grid = stats_grid(nbits, d.num_cus, ctx->stats_grid);
-  int32_t rc;
-  if ((rc = stats_acquire(d, grid, n, d.stream, res))) return rc;
-  hipError_t e = hipSuccess;
-  for (uint32_t i = 0; i < n && e == hipSuccess; ++i)
-    e = launch_stats(g[i], nbits, masks[i], patterns, npatterns, *res + (uint64_t)i * DSE_STATS_WORDS,
-                     d.stats_scratch.buf.ptr, grid, d.stream);
-  if (e != hipSuccess) {
-    (void)release_scratch(&d.stats_scratch, d.stream);
-    return fail(DSE_EHIP, std::string("stats launch failed: ") + hipGetErrorString(e));
-  }
-  return DSE_OK;
-}
-
-// the results of stats_enqueue to the host; drains d.stream and releases the scratch
-int32_t stats_collect(DevState& d, const uint64_t* res, uint32_t n, dse_stats* out) {
-  hipError_t e = hipMemcpyAsync(out, res, (uint64_t)n * sizeof(dse_stats), hipMemcpyDeviceToHost, d.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-  const hipError_t r = release_scratch(&d.stats_scratch, d.stream);
-  if (e == hipSuccess) e = r;
-  if (e != hipSuccess) return fail(DSE_EHIP, std::string("stats copy failed: ") + hipGetErrorString(e));
-  return DSE_OK;
-}
-
 // bit q of the 128 candidates around a seam: a's last 64 (its last at q = 63), then b's first 64
 inline bool seam_bit(const dse_stats& a, const dse_stats& b, uint32_t q) {
   return q < 64 ? (a.tail >> q) & 1 : (b.head >> (q - 64)) & 1;
@@ -85,12 +45,10 @@ extern "C" int32_t dse_stats_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t 
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t s = (hipStream_t)stream;
   const uint32_t grid = stats_grid(nbits, d.num_cus, ctx->stats_grid);
-  if ((rc = stats_acquire(d, grid, 0, s, nullptr))) return rc;
-  const hipError_t e = launch_stats(g_start, nbits, mask_dev, patterns, npatterns,
-                                    reinterpret_cast<uint64_t*>(stats_dev), d.stats_scratch.buf.ptr, grid, s);
-  HIP_TRY(release_scratch(&d.stats_scratch, s));  // also after a failure: what was launched may read the scratch
-  if (e != hipSuccess) return fail(DSE_EHIP, std::string("stats launch failed: ") + hipGetErrorString(e));
-  return DSE_OK;
+  return scratch_launch(d.stats_scratch, stats_scratch_bytes(grid), s, "stats launch", [&](void* slabs) {
+    return launch_stats(g_start, nbits, mask_dev, patterns, npatterns, reinterpret_cast<uint64_t*>(stats_dev), slabs,
+                        grid, s);
+  });
 }
 
 extern "C" int32_t dse_stats_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint32_t* patterns,
@@ -102,11 +60,18 @@ extern "C" int32_t dse_stats_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbit
   DevState& d = ctx->devs[0];
   if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
   HIP_TRY(hipSetDevice(d.device));
+  const uint32_t grid = stats_grid(nbits, d.num_cus, ctx->stats_grid);
   uint64_t* res;
-  uint64_t* const mask = d.scratch_mask.as<uint64_t>();
-  if ((rc = stats_enqueue(ctx, d, &g_start, nbits, &mask, 1, patterns, npatterns, &res))) return rc;
+  if ((rc = result_acquire(d, d.stats_scratch, stats_scratch_bytes(grid), 1, sizeof(dse_stats), 0, &res, nullptr)))
+    return rc;
+  const hipError_t e = launch_stats(g_start, nbits, d.scratch_mask.as<uint64_t>(), patterns, npatterns, res,
+                                    d.stats_scratch.buf.ptr, grid, d.stream);
+  if (e != hipSuccess) {
+    (void)release_scratch(&d.stats_scratch, d.stream);
+    return fail(DSE_EHIP, std::string("stats launch failed: ") + hipGetErrorString(e));
+  }
   dse_stats tmp;
-  if ((rc = stats_collect(d, res, 1, &tmp))) return rc;
+  if ((rc = result_collect(d, d.stats_scratch, "stats", res, sizeof tmp, &tmp))) return rc;
   *out = tmp;
   return DSE_OK;
 }
@@ -116,55 +81,28 @@ extern "C" int32_t dse_stats_resident(dse_ctx* ctx, int32_t my_num, const uint32
   if (!ctx || !out) return fail(DSE_EINVAL, "null ctx or out");
   int32_t rc;
   if ((rc = stats_check_patterns(patterns, npatterns))) return rc;
+  int32_t k0, k1;
+  if ((rc = resident_span(ctx, my_num, "stats", &k0, &k1))) return rc;
   const ResidentSet& r = ctx->resident;
-  if (!r.valid || my_num < 0 || my_num > r.P)
-    return fail(DSE_EINVAL, "chunk " + std::to_string(my_num) + " is not resident");
   const uint64_t cs = (uint64_t)r.cs;
-  const int32_t k0 = my_num ? my_num : 1, k1 = my_num ? my_num : r.P;
-  if ((rc = check_mask_range("stats", (uint64_t)(k1 - 1) * cs, cs))) return rc;
-
-  // every device's chunks are enqueued on its stream before any result is waited for
-  const size_t nd = ctx->devs.size();
-  std::vector<std::vector<uint64_t>> g(nd);
-  std::vector<std::vector<uint64_t*>> masks(nd);
-  std::vector<std::vector<int32_t>> chunk(nd);
-  for (int32_t k = k0; k <= k1; ++k) {
-    const size_t i = (size_t)(k - 1) % nd;
-    g[i].push_back((uint64_t)(k - 1) * cs);
-    masks[i].push_back(r.masks[k - 1].as<uint64_t>());
-    chunk[i].push_back(k);
-  }
-  std::vector<uint64_t*> res(nd, nullptr);
-  std::vector<bool> queued(nd, false);
-  rc = DSE_OK;
-  for (size_t i = 0; i < nd && !rc; ++i) {
-    if (g[i].empty()) continue;
-    DevState& d = ctx->devs[i];
-    if (hipSetDevice(d.device) != hipSuccess) {
-      rc = fail(DSE_EHIP, "hipSetDevice failed");
-      break;
-    }
-    rc = stats_enqueue(ctx, d, g[i].data(), cs, masks[i].data(), (uint32_t)g[i].size(), patterns, npatterns, &res[i]);
-    queued[i] = !rc;
-  }
-  std::vector<dse_stats> parts((size_t)(k1 - k0 + 1));
-  std::vector<dse_stats> got;
-  for (size_t i = 0; i < nd; ++i) {  // collect what was enqueued, also after a failure: the scratch must be released
-    if (!queued[i]) continue;
-    DevState& d = ctx->devs[i];
-    (void)hipSetDevice(d.device);
-    got.resize(g[i].size());
-    const int32_t r2 = stats_collect(d, res[i], (uint32_t)g[i].size(), got.data());
-    if (r2 && !rc) rc = r2;
-    if (!r2)
-      for (size_t j = 0; j < got.size(); ++j) parts[(size_t)(chunk[i][j] - k0)] = got[j];
-  }
-  if (rc) return rc;
-  dse_stats acc = parts[0];
-  for (size_t j = 1; j < parts.size(); ++j)
-    if ((rc = dse_stats_merge(&acc, &parts[j], &acc))) return rc;
-  *out = acc;
-  return DSE_OK;
+  return resident_reduce<dse_stats>(
+      ctx, k0, k1, &DevState::stats_scratch, "stats",
+      [&](DevState& d, const std::vector<int32_t>& chunks, uint64_t** res, bool* acquired) -> int32_t {
+        const uint32_t n = (uint32_t)chunks.size(), grid = stats_grid(cs, d.num_cus, ctx->stats_grid);
+        StreamScratch& s = d.stats_scratch;
+        int32_t ra = result_acquire(d, s, stats_scratch_bytes(grid), n, sizeof(dse_stats), 0, res, nullptr);
+        if (ra) return ra;
+        *acquired = true;
+        hipError_t e = hipSuccess;
+        for (uint32_t j = 0; j < n && e == hipSuccess; ++j) {
+          const size_t c = (size_t)chunks[j] - 1;
+          e = launch_stats((uint64_t)c * cs, cs, r.masks[c].as<uint64_t>(), patterns, npatterns,
+                           *res + (uint64_t)j * DSE_STATS_WORDS, s.buf.ptr, grid, d.stream);
+        }
+        if (e != hipSuccess) return fail(DSE_EHIP, std::string("stats launch failed: ") + hipGetErrorString(e));
+        return DSE_OK;
+      },
+      dse_stats_merge, out);
 }
 
 extern "C" int32_t dse_stats_merge(const dse_stats* a, const dse_stats* b, dse_stats* out) {
