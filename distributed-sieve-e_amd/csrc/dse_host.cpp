@@ -920,6 +920,16 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     *value = (int64_t)kMaskTileBits;
   } else if (n == "query_index_builds") {
     *value = ctx->query_index_builds;
+  } else if (n == "wheel_ta") {
+    *value = (int64_t)wheel_consts().ta;
+  } else if (n == "wheel_tb1") {
+    *value = (int64_t)wheel_consts().tb1;
+  } else if (n == "wheel_tb") {
+    *value = (int64_t)wheel_consts().tb;
+  } else if (n == "wheel_max_prime") {
+    *value = (int64_t)wheel_consts().max_prime;
+  } else if (n == "wheel_log_kp") {
+    *value = (int64_t)wheel_consts().log_kp;
   } else {
     return fail(DSE_EINVAL, "unknown stat " + n);
   }
@@ -939,6 +949,26 @@ int32_t dse_debug_finish_format(uint64_t v, uint32_t flags, char out[32]) {
   if (!out) return fail(DSE_EINVAL, "null out");
   if (flags & ~DSE_FINISH_DOUBLES) return fail(DSE_EINVAL, "only DSE_FINISH_DOUBLES applies to one value");
   return (int32_t)fin_format_value(v, flags & DSE_FINISH_DOUBLES, 0u, [&](uint32_t p, char c) { out[p] = c; });
+}
+
+int32_t dse_debug_wheel_arith_dev(dse_ctx* ctx, uint32_t op, const uint64_t* x_dev, const uint64_t* y_dev, uint64_t n,
+                                  uint64_t* out_dev, void* stream) {
+  if (!ctx) return fail(DSE_EINVAL, "null ctx");
+  if (op >= kArithOps) return fail(DSE_EINVAL, "unknown wheel arithmetic op");
+  static_assert(kArithKbModF32 == DSE_ARITH_KBMOD_F32 && kArithKbModF38 == DSE_ARITH_KBMOD_F38 &&
+                    kArithKbModBarrett == DSE_ARITH_KBMOD_BARRETT && kArithModBarrett == DSE_ARITH_MOD_BARRETT &&
+                    kArithBarrettFactor == DSE_ARITH_BARRETT_FACTOR && kArithDivSmall == DSE_ARITH_DIV_SMALL &&
+                    kArithDivCeilSmall == DSE_ARITH_DIV_CEIL_SMALL && kArithMulmodSmall == DSE_ARITH_MULMOD_SMALL &&
+                    kArithPlaneFirst == DSE_ARITH_PLANE_FIRST && kArithFirstAtOrAfter == DSE_ARITH_FIRST_AT_OR_AFTER &&
+                    kArithOps == DSE_ARITH_FIRST_AT_OR_AFTER + 1,
+                "include/dse.h DSE_ARITH_* are the probe's ops");
+  if (n > 0 && (!x_dev || !y_dev || !out_dev)) return fail(DSE_EINVAL, "null x_dev, y_dev or out_dev");
+  if ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(y_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 7u)
+    return fail(DSE_EINVAL, "x_dev, y_dev or out_dev is not 8-byte aligned");
+  if (n == 0) return DSE_OK;
+  HIP_TRY(hipSetDevice(ctx->devs[0].device));
+  HIP_TRY(launch_arith_probe(op, x_dev, y_dev, n, out_dev, ctx->devs[0].num_cus, (hipStream_t)stream));
+  return DSE_OK;
 }
 
 }  // extern "C"

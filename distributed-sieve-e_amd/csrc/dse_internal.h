@@ -1,6 +1,7 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
-// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip) and the C-ABI host layer (dse_host.cpp,
+// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip, and the test-only dse_arith_probe.hip)
+// and the C-ABI host layer (dse_host.cpp,
 // dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp, dse_query_host.cpp,
 // dse_goldbach_host.cpp). Not installed;
 // include/dse.h is the ABI. The units that read a resident mask (finish,
@@ -210,6 +211,30 @@ hipError_t launch_wheel_bucketed(const void* table, const WheelArgs& wa, int num
 // Fill the Barrett factors m[] and wheel offsets a[] of a table whose p[] is final.
 // n_hint: table capacity when known (sizes the grid: about 4 primes per thread)
 hipError_t launch_wheel_offsets(void* table, int num_cus, hipStream_t stream, uint64_t n_hint = 0);
+
+// Test-only (dse_arith_probe.hip): out[i] = op(x[i], y[i]), i < n, by the wheel
+// kernel's own integer helpers (dse_wheel_kernel.h); op = kArith*, the
+// DSE_ARITH_* of include/dse.h. And the thresholds of the wheel kernel's units as the library was built.
+enum : uint32_t {
+  kArithKbModF32 = 0,
+  kArithKbModF38,
+  kArithKbModBarrett,
+  kArithModBarrett,
+  kArithBarrettFactor,
+  kArithDivSmall,
+  kArithDivCeilSmall,
+  kArithMulmodSmall,
+  kArithPlaneFirst,
+  kArithFirstAtOrAfter,
+  kArithOps
+};
+hipError_t launch_arith_probe(uint32_t op, const uint64_t* x, const uint64_t* y, uint64_t n, uint64_t* out,
+                              int num_cus, hipStream_t stream);
+struct WheelConsts {
+  uint32_t ta, tb1, tb, log_kp;  // A/B1, B1/B2 and B2/L thresholds; log2 of a full segment's periods
+  uint64_t max_prime;            // kWheelMaxPrime
+};
+WheelConsts wheel_consts();
 
 // Device finish (dse_finish.hip): the set bits of mask (odd indices [g_start,
 // g_start + nbits), 64-bit words) as the slice of a primes{k}.txt file whose

@@ -271,6 +271,21 @@ __host__ __device__ __forceinline__ uint32_t mod_barrett(uint64_t x, uint32_t p,
   return (uint32_t)r;
 }
 
+// floor((2^64-1)/p) for 2 <= p < 2^32 without a 64-bit division: a double
+// quotient (relative error 2^-52, so off by < 2^11) corrected by the exact
+// remainder, itself below 2^43 in magnitude and so exact in a double.
+__device__ __forceinline__ uint64_t barrett_factor(uint32_t p) {
+  const double dp = (double)p;
+  uint64_t m = (uint64_t)(18446744073709551615.0 / dp);        // rounds 2^64-1 up to 2^64: may overshoot
+  if (m > ~0ull / 2) m = ~0ull / 2;                              // p >= 2: the true m < 2^63
+  int64_t r = (int64_t)(~0ull - m * (uint64_t)p);                // true remainder + (true m - m) * p
+  m += (int64_t)__builtin_floor((double)r / dp);
+  r = (int64_t)(~0ull - m * (uint64_t)p);
+  while (r < 0) { --m; r += p; }
+  while (r >= (int64_t)p) { ++m; r -= p; }
+  return m;
+}
+
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 // ceil(t / p), t < 2^24
@@ -563,6 +578,51 @@ static_assert(kWheelMaxPrime < (1ull << 23), "__mul24 / __umul24 operands and fl
 static_assert((uint64_t)(kWheelMaxPrime + 1) * (kWheelMaxPrime + 1) / 30 < (1ull << 38),
               "ranges without bucketed primes never need the Barrett path (unit_L<false>)");
 
+// kb mod p for kb < 2^32 (values below 1.29e11), TB < p <= kWheelMaxPrime,
+// invp = fast_rcp((float)p). A float quotient is within one of the true one:
+// its relative error is below 2^-22 (kb rounded to float 2^-24, the rcp
+// 2^-23, the product 2^-24) and q < 2^32 / p < 2^22 for p > TB (kQuotBits), so
+// |error| < 1, and the truncation adds at most one more: kb - q p is in
+// [-p, 2p), corrected by two unsigned min steps.
+__device__ __forceinline__ uint32_t kb_mod_p_f32(uint32_t kb, uint32_t p, float invp) {
+  const uint32_t q = (uint32_t)((float)kb * invp);
+  // q p by v_mul_u32_u24 as asm: written as __umul24 the compiler merged it
+  // with the other path's product into one quarter-rate v_mul_lo_u32
+  uint32_t qp;
+  asm("v_mul_u32_u24 %0, %1, %2" : "=v"(qp) : "v"(q), "v"(p));
+  uint32_t x = kb - qp;  // in [-p, 2p) as a signed value; p < 2^24
+  x = min(x, x + p);
+  return min(x, x - p);
+}
+
+// Kb mod p for Kb < 2^38 (values below 8.2e12), p and invp as above: the float
+// quotient of Kb is within kQuotErr38 of the true one (relative error <
+// 2^-22, Kb / p < 2^38 / (TB + 1)), so Kb - q p is exact in 32 bits (|.| <
+// (kQuotErr38 + 1) p < 2^31, asserted above); one more float quotient of that
+// rest leaves it in [-p, 2p). 12 VALU where the 64-bit Barrett reduction
+// takes ~24.
+__device__ __forceinline__ uint32_t kb_mod_p_f38(uint64_t Kb, uint32_t p, float invp) {
+  const uint32_t q = (uint32_t)((float)Kb * invp);
+  const int32_t r = (int32_t)((uint32_t)Kb - q * p);
+  const int32_t q2 = (int32_t)((float)r * invp);
+  uint32_t x = (uint32_t)(r - __mul24(q2, (int32_t)p));
+  x = min(x, x + p);
+  return min(x, x - p);
+}
+
+// Kb mod p as unit_L takes it (Kb is wave-uniform there): one float quotient
+// while Kb < 2^32, two below 2^38, and above that, which only a launch with
+// bucketed primes meets (BARRETT), the 64-bit Barrett reduction with m =
+// floor((2^64-1)/p). Without BARRETT m is not read and Kb must be below 2^38.
+// dse_arith_probe.hip runs these three functions against exact integers
+// (tests/test_gpu_wheel_arith.py).
+template <bool BARRETT>
+__device__ __forceinline__ uint32_t kb_mod_p(uint64_t Kb, uint32_t p, float invp, uint64_t m) {
+  if (Kb < (1ull << 32)) return kb_mod_p_f32((uint32_t)Kb, p, invp);
+  if (!BARRETT || Kb < (1ull << 38)) return kb_mod_p_f38(Kb, p, invp);
+  return mod_barrett(Kb, p, m);
+}
+
 // L: 64 large primes (p > TB), one per lane; at step q lane L handles the
 // absolute residue (q + L) & 7 (a half-wave spreads over all 8 planes). The
 // per-plane hit count is at most ceil(KP / pmin): units whose primes all
@@ -703,37 +763,7 @@ __device__ __forceinline__ void unit_L(const LargeOps& o, uint64_t Vs, uint64_t 
                                        uint32_t sqrt_vs) {
   const uint32_t p = o.p & kLPrimeMask;  // the prime (>= 2^31: a lane past the table end)
   const float invp = fast_rcp((float)p);
-  // Kb mod p. While Kb < 2^32 (values below 1.29e11; wave-uniform) a float
-  // quotient is within one of the true one: its relative error is below
-  // 2^-22 (Kb rounded to float 2^-24, the rcp 2^-23, the product 2^-24) and
-  // q < 2^32 / p < 2^22 for p > TB (kQuotBits), so |error| < 1, and the
-  // truncation adds at most one more: Kb - q p is in (-p, 2p), corrected by
-  // two unsigned min steps; the 64-bit Barrett reduction covers Kb >= 2^38.
-  uint32_t kbm;
-  if (Kb < (1ull << 32)) {
-    const uint32_t q = (uint32_t)((float)(uint32_t)Kb * invp);
-    // q p by v_mul_u32_u24 as asm: written as __umul24 the compiler merged it
-    // with the other path's product into one quarter-rate v_mul_lo_u32
-    uint32_t qp;
-    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(qp) : "v"(q), "v"(p));
-    uint32_t x = (uint32_t)Kb - qp;  // in (-p, 2p) as a signed value; p < 2^24
-    x = min(x, x + p);
-    kbm = min(x, x - p);
-  } else if (!BARRETT || Kb < (1ull << 38)) {
-    // values below 8.2e12: the float quotient of Kb is within kQuotErr38 of
-    // the true one (relative error < 2^-22, Kb / p < 2^38 / (TB + 1)), so
-    // Kb - q p is exact in 32 bits (|.| < (kQuotErr38 + 1) p < 2^31, asserted
-    // below); one more float quotient of that rest leaves it in (-p, 2p). 12
-    // VALU where the 64-bit Barrett reduction takes ~24.
-    const uint32_t q = (uint32_t)((float)Kb * invp);
-    const int32_t r = (int32_t)((uint32_t)Kb - q * p);
-    const int32_t q2 = (int32_t)((float)r * invp);
-    uint32_t x = (uint32_t)(r - __mul24(q2, (int32_t)p));
-    x = min(x, x + p);
-    kbm = min(x, x - p);
-  } else {
-    kbm = mod_barrett(Kb, p, o.m);
-  }
+  const uint32_t kbm = kb_mod_p<BARRETT>(Kb, p, invp, o.m);
   const uint32_t nKbm = 0u - kbm;
   const uint32_t pmax = __builtin_amdgcn_readlane(p, 63);
   // some lane not live or with p^2 inside the segment: the set's primes

@@ -101,7 +101,12 @@ SIGNATURES = {
     "dse_debug_init_logical": (_vp, [_i32]),
     "dse_debug_get_stat": (_i32, [_vp, _cp, _pi64]),
     "dse_debug_expand_block": (_i32, [_i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "dse_debug_wheel_arith_dev": (_i32, [_vp, _u32, _vp, _vp, _u64, _vp, _vp]),
 }
+
+# include/dse.h DSE_ARITH_*: the ops of dse_debug_wheel_arith_dev
+(ARITH_KBMOD_F32, ARITH_KBMOD_F38, ARITH_KBMOD_BARRETT, ARITH_MOD_BARRETT, ARITH_BARRETT_FACTOR, ARITH_DIV_SMALL,
+ ARITH_DIV_CEIL_SMALL, ARITH_MULMOD_SMALL, ARITH_PLANE_FIRST, ARITH_FIRST_AT_OR_AFTER) = range(10)
 
 _lib = None
 

@@ -299,6 +299,12 @@ class Context:
         check(lib().dse_debug_get_stat(self.ptr, name.encode(), ctypes.byref(v)), "dse_debug_get_stat")
         return v.value
 
+    def debug_wheel_arith_dev(self, op: int, x_ptr: int, y_ptr: int, n: int, out_ptr: int, stream_ptr: int = 0):
+        """Test-only: out[i] = op(x[i], y[i]) by the wheel kernel's own integer
+        helpers, on device uint64 arrays (include/dse.h dse_debug_wheel_arith_dev)."""
+        check(lib().dse_debug_wheel_arith_dev(self.ptr, op, x_ptr or None, y_ptr or None, n, out_ptr or None,
+                                              stream_ptr or None), "dse_debug_wheel_arith_dev")
+
     # -- device-buffer entry points (torch tensors' data_ptr()) --------------
     def base_primes_dev_async(self, limit: int, table_ptr: int, table_bytes: int, stream_ptr: int = 0):
         check(lib().dse_base_primes_dev_async(self.ptr, limit, table_ptr, table_bytes, stream_ptr or None),

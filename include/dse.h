@@ -543,7 +543,13 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   "stats_tile_bits": candidates per tile of the dse_stats_* kernels;
  *   "query_index_builds": rank indices dse_query_resident has built for
  *   resident chunks so far (one per chunk and dse_sieve_all that replaced the
- *   masks).
+ *   masks);
+ *   "wheel_ta", "wheel_tb1", "wheel_tb": the wheel kernel's unit thresholds as
+ *   built (a prime p > 79 is marked by an A unit up to wheel_ta, a B1 unit up
+ *   to wheel_tb1, a B2 unit up to wheel_tb, an L unit above);
+ *   "wheel_max_prime": the largest prime the wheel kernel marks itself (the
+ *   table's m[], a[] and pl[] are filled up to it; larger primes are bucketed);
+ *   "wheel_log_kp": log2 of the periods of 30 integers in a full segment.
  * The "plan_*" names describe what the context's most recent sieving entry
  * point (dse_sieve_odd_range, dse_sieve_chunk, dse_sieve_all, dse_sieve_window,
  * dse_sieve_range_dev_async, and the calls that sieve a range before they
@@ -626,6 +632,47 @@ int32_t dse_debug_query_host(const uint64_t *mask, uint64_t g_start, uint64_t nb
 int32_t dse_debug_goldbach_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits,
                                 const uint64_t *below, uint32_t below_shift, uint64_t below_bits,
                                 uint32_t nprimes, dse_goldbach *out);
+
+/* The wheel kernel's integer helpers, run elementwise on the device by the
+ * functions the kernels themselves call: out_dev[i] = op(x_dev[i], y_dev[i])
+ * for i < n, enqueued on `stream`; y is always the modulus p, and the float
+ * reciprocal the helpers take is formed from p as the kernel's units form it.
+ * With TB = "wheel_tb" and PMAX = "wheel_max_prime" of dse_debug_get_stat, the
+ * ops and their domains (outside a domain the result is unspecified; the call
+ * reads and writes only the n words of each array whatever they hold):
+ *   KBMOD_F32      x mod p by one float quotient: x < 2^32 (the low 32 bits of
+ *                  x are reduced whatever the rest holds), TB < p <= PMAX;
+ *   KBMOD_F38      x mod p as the launches without bucketed primes reduce it
+ *                  (one float quotient below 2^32, two above): x < 2^38,
+ *                  TB < p <= PMAX;
+ *   KBMOD_BARRETT  x mod p as the bucketed launches reduce it (the two above,
+ *                  the 64-bit Barrett reduction from 2^38 on): x < 2^63,
+ *                  TB < p <= PMAX;
+ *   MOD_BARRETT    x mod p by the Barrett reduction: x < 2^63, 2 <= p < 2^32;
+ *   BARRETT_FACTOR floor((2^64 - 1) / p), the factor the two ops above compute
+ *                  for themselves: 2 <= p < 2^32 (x is read and ignored);
+ *   DIV_SMALL      floor(x / p), DIV_CEIL_SMALL ceil(x / p): x < 2^24,
+ *                  7 <= p <= TB;
+ *   MULMOD_SMALL   a b mod p, x = a | b << 32: a, b < p, 7 <= p <= TB;
+ *   PLANE_FIRST    the smallest k >= 0 with p | Xs + rho + 30k, x = Xs | rho << 32:
+ *                  Xs < p, rho < 30, 7 <= p <= TB coprime to 30;
+ *   FIRST_AT_OR_AFTER the smallest k >= start with k = kp (mod p),
+ *                  x = kp | start << 32: kp < p, start < 2^23, 7 <= p <= TB.
+ * A y below 2 or above 2^32 - 1 gives 0 for every op. Test-only; n = 0 launches
+ * nothing. DSE_EINVAL for a null ctx, an unknown op, a null pointer with n > 0
+ * or a pointer that is not 8-byte aligned. */
+#define DSE_ARITH_KBMOD_F32 0u
+#define DSE_ARITH_KBMOD_F38 1u
+#define DSE_ARITH_KBMOD_BARRETT 2u
+#define DSE_ARITH_MOD_BARRETT 3u
+#define DSE_ARITH_BARRETT_FACTOR 4u
+#define DSE_ARITH_DIV_SMALL 5u
+#define DSE_ARITH_DIV_CEIL_SMALL 6u
+#define DSE_ARITH_MULMOD_SMALL 7u
+#define DSE_ARITH_PLANE_FIRST 8u
+#define DSE_ARITH_FIRST_AT_OR_AFTER 9u
+int32_t dse_debug_wheel_arith_dev(dse_ctx *ctx, uint32_t op, const uint64_t *x_dev, const uint64_t *y_dev,
+                                  uint64_t n, uint64_t *out_dev, void *stream);
 
 #ifdef __cplusplus
 }
