@@ -4,7 +4,8 @@
 // and residency checks, scratch growth, the result scratch and per-device fan-out
 // of resident chunks, the two-slot slab pipe). The finish side is
 // dse_finish_host.cpp, primes as numbers dse_primes_host.cpp, statistics
-// dse_stats_host.cpp, rank and select dse_query_host.cpp, Goldbach dse_goldbach_host.cpp.
+// dse_stats_host.cpp, rank and select dse_query_host.cpp, Goldbach dse_goldbach_host.cpp,
+// residue classes and races dse_race_host.cpp.
 //
 // Replaces the reference's orchestration of the hot path:
 //   spread-work (sieve.clj:15-34)            -> dse_spread_work (exact int64)
@@ -530,6 +531,7 @@ const struct {
     {"stats_grid", 0, (int64_t)kStatsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->stats_grid = (uint32_t)v; }},
     {"query_grid", 0, (int64_t)kQueryMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->query_grid = (uint32_t)v; }},
     {"goldbach_grid", 0, (int64_t)kGbMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->goldbach_grid = (uint32_t)v; }},
+    {"race_grid", 0, (int64_t)kRaceMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->race_grid = (uint32_t)v; }},
 };
 
 }  // namespace
@@ -642,6 +644,7 @@ void dse_destroy(dse_ctx* ctx) {
     (void)free_scratch(&d.stats_scratch);
     (void)free_scratch(&d.query_scratch);
     (void)free_scratch(&d.goldbach_scratch);
+    (void)free_scratch(&d.race_scratch);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }

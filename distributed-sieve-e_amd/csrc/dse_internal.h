@@ -1,13 +1,13 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
-// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip, and the test-only dse_arith_probe.hip)
+// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip, dse_race.hip, and the test-only dse_arith_probe.hip)
 // and the C-ABI host layer (dse_host.cpp,
 // dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp, dse_query_host.cpp,
-// dse_goldbach_host.cpp). Not installed;
+// dse_goldbach_host.cpp, dse_race_host.cpp). Not installed;
 // include/dse.h is the ABI. The units that read a resident mask (finish,
-// primes, stats, query, goldbach) share its range, tiles and clipped word load (dse_mask.h);
+// primes, stats, query, goldbach, race) share its range, tiles and clipped word load (dse_mask.h);
 // every unit with a workgroup sum, scan or best-of takes it from dse_block.h; the two that reduce
-// a range to one struct through per-workgroup slabs (stats, goldbach) share dse_slab.h.
+// a range to one struct through per-workgroup slabs (stats, goldbach, race) share dse_slab.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -302,5 +302,17 @@ uint64_t goldbach_scratch_bytes(uint32_t grid);
 hipError_t launch_goldbach(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint32_t mask_shift,
                            const uint64_t* below, uint32_t below_shift, uint64_t below_bits, uint32_t nprimes,
                            uint64_t* out, void* slabs, uint32_t grid, hipStream_t stream);
+
+// Residue-class counts and a prime race of a mask (dse_race.hip): the launches of a slab reduction
+// (dse_slab.h) with a count pass in front, which write the dse_race (kRaceWords uint64 words,
+// dse_race_word.h) at `out`: the counts of the classes mod q (3..64) and, for a != b (both < q), the
+// race of class a against class b from d_start; a == b (with d_start 0) runs the count and closing
+// launches only. grid = race_grid(nbits, CUs of the device, cap or 0): slab_grid's rule. slabs:
+// race_scratch_bytes(grid) bytes of device scratch.
+constexpr uint32_t kRaceMaxGrid = 1024;
+uint32_t race_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
+uint64_t race_scratch_bytes(uint32_t grid);
+hipError_t launch_race(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint32_t q, uint32_t a, uint32_t b,
+                       int64_t d_start, uint64_t* out, void* slabs, uint32_t grid, hipStream_t stream);
 
 }  // namespace dse

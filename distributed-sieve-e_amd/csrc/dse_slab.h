@@ -1,5 +1,6 @@
 // dse_slab.h -- the two-launch slab reduction of the units that turn a whole mask
-// range into one small struct (dse_stats.hip, dse_goldbach.hip). Main launch: `grid`
+// range into one small struct (dse_stats.hip, dse_goldbach.hip; dse_race.hip puts a
+// count launch over the same runs in front). Main launch: `grid`
 // workgroups, each walking its own contiguous run of tiles (dse_mask.h) and ending
 // with one slab of plain stores: scalars of the unit's own, the number of histogram
 // bins it filled (word kSlBins) and those bins (from word kSlHist). Closing launch:

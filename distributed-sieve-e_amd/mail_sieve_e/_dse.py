@@ -34,6 +34,9 @@ STATS_WORDS, STATS_GAP_BINS, STATS_MAX_PATTERNS, STATS_NONE = 27 + 1024, 1024, 8
 # include/dse.h dse_goldbach as uint64 words: 8 scalar members, then hist[2048]
 GOLDBACH_PRIMES, GOLDBACH_WORDS, GOLDBACH_NONE = 2048, 8 + 2048, (1 << 64) - 1
 
+# include/dse.h dse_race as uint64 words: 17 scalar members, then counts[64]
+RACE_MAX_MODULUS, RACE_WORDS, RACE_NONE = 64, 17 + 64, (1 << 64) - 1
+
 # include/dse.h DSE_QUERY_*
 QUERY_NONE = (1 << 64) - 1
 QUERY_RANK, QUERY_SELECT, QUERY_NEXT, QUERY_PREV, QUERY_TEST = range(5)
@@ -92,6 +95,11 @@ SIGNATURES = {
     "dse_goldbach_range": (_i32, [_vp, _u64, _u64, _u32, _pu64]),
     "dse_goldbach_resident": (_i32, [_vp, _i32, _u32, _pu64]),
     "dse_goldbach_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_race_dev_async": (_i32, [_vp, _u64, _u64, _vp, _u32, _u32, _u32, _i64, _vp, _vp]),
+    "dse_race_range": (_i32, [_vp, _u64, _u64, _u32, _u32, _u32, _i64, _pu64]),
+    "dse_race_resident": (_i32, [_vp, _i32, _u32, _u32, _u32, _i64, _pu64]),
+    "dse_race_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_debug_race_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _u32, _i64, _pu64]),
     "dse_debug_goldbach_host": (_i32, [_pu64, _u64, _u64, _pu64, _u32, _u64, _u32, _pu64]),
     "dse_debug_query_host": (_i32, [_pu64, _u64, _u64, _u32, _pu64, _u64, _pu64]),
     "dse_debug_stats_host": (_i32, [_pu64, _u64, _u64, _pu32, _u32, _pu64]),

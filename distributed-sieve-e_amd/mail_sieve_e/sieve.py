@@ -204,6 +204,76 @@ def goldbach_host(mask: np.ndarray, g_start: int, nbits: int, below: Optional[np
     return Goldbach(out)
 
 
+class Race:
+    """One dse_race (include/dse.h "residue classes and races"): the entries of the
+    odd candidates [g_start, g_start + nbits) per class mod q, and the race of class
+    a against class b from d_start. ``words`` is the struct as its uint64 words."""
+
+    def __init__(self, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.shape != (_dse.RACE_WORDS,):
+            raise ValueError("a dse_race is %d uint64 words" % _dse.RACE_WORDS)
+        self.words = w
+
+    def _signed(self, i):
+        v = int(self.words[i])
+        return v - (1 << 64) if v >> 63 else v
+
+    def _value(self, i):
+        g = int(self.words[i])
+        return None if g == _dse.RACE_NONE else 3 + 2 * g
+
+    g_start = property(lambda s: int(s.words[0]))
+    nbits = property(lambda s: int(s.words[1]))
+    q = property(lambda s: int(s.words[2]))
+    a = property(lambda s: int(s.words[3]))
+    b = property(lambda s: int(s.words[4]))
+    d_start = property(lambda s: s._signed(5))
+    d_end = property(lambda s: s._signed(6))
+    steps = property(lambda s: int(s.words[7]))
+    a_ahead = property(lambda s: int(s.words[8]))
+    b_ahead = property(lambda s: int(s.words[9]))
+    ties = property(lambda s: int(s.words[10]))
+    first_a_ahead = property(lambda s: s._value(11), doc="value of the first step after which D > 0, or None")
+    first_b_ahead = property(lambda s: s._value(12), doc="value of the first step after which D < 0, or None")
+    max_d = property(lambda s: s._signed(13))
+    max_at = property(lambda s: s._value(14), doc="value of the first step that attains max_d, or None")
+    min_d = property(lambda s: s._signed(15))
+    min_at = property(lambda s: s._value(16), doc="value of the first step that attains min_d, or None")
+
+    @property
+    def counts(self) -> np.ndarray:
+        """uint64[q]: counts[r] = entries whose value is r mod q."""
+        return self.words[17:17 + self.q]
+
+    def merge(self, other: "Race") -> "Race":
+        """The result of this range followed by the adjacent ``other``, which started
+        from this one's d_end (dse_race_merge)."""
+        out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
+        check(lib().dse_race_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_race_merge")
+        return Race(out)
+
+    def __eq__(self, other):
+        return isinstance(other, Race) and np.array_equal(self.words, other.words)
+
+    def __repr__(self):
+        return (f"Race(g_start={self.g_start}, nbits={self.nbits}, q={self.q}, a={self.a}, b={self.b}, "
+                f"d_start={self.d_start}, d_end={self.d_end}, steps={self.steps}, a_ahead={self.a_ahead}, "
+                f"b_ahead={self.b_ahead}, ties={self.ties}, first_a_ahead={self.first_a_ahead}, "
+                f"first_b_ahead={self.first_b_ahead}, max_d={self.max_d} at {self.max_at}, "
+                f"min_d={self.min_d} at {self.min_at})")
+
+
+def race_host(mask: np.ndarray, g_start: int, nbits: int, q: int, a: int, b: int, d_start: int = 0) -> Race:
+    """Test-only: the race kernels' per-word bodies run on the host over a host mask
+    (include/dse.h dse_debug_race_host)."""
+    out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    check(lib().dse_debug_race_host(u64p(m) if len(m) else None, g_start, nbits, q, a, b, d_start, u64p(out)),
+          "dse_debug_race_host")
+    return Race(out)
+
+
 class Context:
     """A libdse context: one process driving ``num_gpus`` devices, or one
     device (``device=``) for one-process-per-GPU ranks. ``logical=k`` (tests
@@ -465,6 +535,41 @@ class Context:
         check(lib().dse_goldbach_resident(self.ptr, 0 if my_num is None else my_num, nprimes, u64p(out)),
               "dse_goldbach_resident")
         return Goldbach(out)
+
+    # -- residue classes and races -------------------------------------------------
+    def race_dev_async(self, g_start: int, nbits: int, mask_ptr: int, q: int, a: int, b: int, d_start: int,
+                       out_ptr: int, stream_ptr: int = 0):
+        """The class counts mod q and the race of class a against class b of a device
+        mask as one dse_race (_dse.RACE_WORDS uint64 words) in device memory at
+        out_ptr (include/dse.h dse_race_dev_async)."""
+        check(lib().dse_race_dev_async(self.ptr, g_start, nbits, mask_ptr or None, q, a, b, d_start, out_ptr or None,
+                                       stream_ptr or None), "dse_race_dev_async")
+
+    def race_range(self, g_start: int, nbits: int, q: int, a: int, b: int, d_start: int = 0) -> Race:
+        """gen-table + sieve-e of an odd-index range and its class counts and race,
+        computed on the device: only the dse_race reaches the host."""
+        out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
+        check(lib().dse_race_range(self.ptr, g_start, nbits, q, a, b, d_start, u64p(out)), "dse_race_range")
+        return Race(out)
+
+    def race_window(self, lo: int, hi: int, q: int, a: int, b: int, d_start: int = 0) -> Race:
+        """The class counts and race of the odd values in [max(lo, 3), hi]
+        (primes_window's convention); an empty window gives the empty result."""
+        x = max(lo, 3) | 1
+        if hi < x:
+            return self.race_range(min((x - 3) // 2, 1 << 62), 0, q, a, b, d_start)
+        y = hi if hi & 1 else hi - 1
+        return self.race_range((x - 3) // 2, (y - x) // 2 + 1, q, a, b, d_start)
+
+    def resident_race(self, my_num: Optional[int] = None, q: int = 4, a: int = 1, b: int = 3,
+                      d_start: int = 0) -> Race:
+        """The class counts and race of a chunk the last sieve_all left on its
+        device, or (my_num=None) of all its chunks as one range: every chunk starts
+        from the d_end of the one before it, and the results are merged in order."""
+        out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
+        check(lib().dse_race_resident(self.ptr, 0 if my_num is None else my_num, q, a, b, d_start, u64p(out)),
+              "dse_race_resident")
+        return Race(out)
 
     # -- rank and select ---------------------------------------------------------
     def query_index_dev_async(self, g_start: int, nbits: int, mask_ptr: int, index_ptr: int, index_bytes: int,

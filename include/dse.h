@@ -483,6 +483,83 @@ int32_t dse_goldbach_resident(dse_ctx *ctx, int32_t my_num, uint32_t nprimes, ds
  * Each side must have been computed with the candidates below it visible (b's `below` = a's tail). */
 int32_t dse_goldbach_merge(const dse_goldbach *a, const dse_goldbach *b, dse_goldbach *out);
 
+/* ---- residue classes and races ---------------------------------------------- */
+
+/* pi(x; q, r) for every class r mod q, and the race between two classes (Chebyshev's bias),
+ * computed on the GPU from a device-resident mask; only the dse_race crosses to the host.
+ *
+ * Entries. An entry is a set bit of the mask; its value is v = 3 + 2 (g_start + bit index). The
+ * prime 2 is in no mask: a race from 3 on that involves its class (2 mod q, q odd) counts it by
+ * starting from d_start = -1 or +1.
+ *
+ * Modulus. 3 <= q <= DSE_RACE_MAX_MODULUS = 64.
+ *
+ * Class counts. counts[r], r < q, is the number of entries with v mod q == r; slots r >= q are 0. A
+ * prime that divides q is counted in its own class like any other: 3 is in class 3 mod 4, and in
+ * class 0 mod 3.
+ *
+ * Race. For residues a != b (both < q) a step is an entry whose value is = a or = b (mod q). D
+ * starts at the caller's d_start (an int64) and goes +1 at every a-step and -1 at every b-step, in
+ * increasing order of value. Every race number is about the value of D after a step of the range:
+ * steps is their number; a_ahead, b_ahead and ties count the steps after which D > 0, D < 0 and
+ * D == 0 (they sum to steps); first_a_ahead and first_b_ahead are the global candidate index g of
+ * the first step after which D > 0 and D < 0, DSE_RACE_NONE if there is none; max_d is the largest
+ * D after a step and max_g the g of the first step that attains it, min_d and min_g likewise; with
+ * no step in the range max_d = min_d = d_start and max_g = min_g = DSE_RACE_NONE; d_end is D after
+ * the last step (d_start if there is none). A class that holds no odd candidate (q = 4, a = 2) is
+ * legal and never steps.
+ *
+ * Counts only. a == b means no race: it requires d_start == 0 (else DSE_EINVAL), only counts[] is
+ * computed, steps, a_ahead, b_ahead, ties, max_d, min_d and d_end are 0, the four positions are
+ * DSE_RACE_NONE, and the race pass is not launched.
+ *
+ * d_start, d_end, max_d and min_d hold an int64 in two's complement. Every member is a uint64_t and
+ * there is no padding: bindings may treat a dse_race as an array of DSE_RACE_WORDS uint64 words. */
+#define DSE_RACE_MAX_MODULUS 64
+#define DSE_RACE_NONE UINT64_MAX
+#define DSE_RACE_WORDS (17 + DSE_RACE_MAX_MODULUS)
+typedef struct dse_race {
+  uint64_t g_start, nbits;             /* the range the numbers are of */
+  uint64_t q, a, b;
+  uint64_t d_start, d_end;             /* int64, two's complement */
+  uint64_t steps, a_ahead, b_ahead, ties;
+  uint64_t first_a_ahead, first_b_ahead;
+  uint64_t max_d, max_g, min_d, min_g; /* *_d int64 */
+  uint64_t counts[DSE_RACE_MAX_MODULUS];
+} dse_race;
+
+/* Async on stream, on a caller-owned device mask (bit c = candidate g_start + c). Every member of
+ * *out_dev (sizeof(dse_race) bytes of device memory, 8-byte aligned) is written and nothing
+ * outside it is touched. Bits past nbits in the last mask word are ignored; nbits = 0 writes the
+ * empty result. DSE_EINVAL for a null ctx or out_dev, a null mask with nbits > 0, a misaligned
+ * mask_dev or out_dev, q outside 3..64, a or b >= q, or a == b with d_start != 0. DSE_ERANGE for
+ * |d_start| > 2^45, a range beyond 2^62 or more than 2^44 candidates in one call. */
+int32_t dse_race_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, const uint64_t *mask_dev,
+                           uint32_t q, uint32_t a, uint32_t b, int64_t d_start, dse_race *out_dev,
+                           void *stream);
+
+/* gen-table + sieve-e + the race of an odd-index range, on the first device; host result. The
+ * range rules of dse_sieve_odd_range apply. */
+int32_t dse_race_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, uint32_t q, uint32_t a,
+                       uint32_t b, int64_t d_start, dse_race *out);
+
+/* The same for chunk my_num left resident by the last dse_sieve_all; my_num = 0: for all P chunks
+ * as the one range [3, 3 + 2 P cs) (dse_stats_resident's convention). Chunk k + 1 starts from chunk
+ * k's d_end, so for several chunks with a != b the chunks' class counts are taken first, on every
+ * device and enqueued before any is waited for; the host forms the running d_start of every chunk,
+ * then every chunk's race is enqueued and the results are merged in chunk order. DSE_EINVAL if the
+ * chunk is not resident. */
+int32_t dse_race_resident(dse_ctx *ctx, int32_t my_num, uint32_t q, uint32_t a, uint32_t b,
+                          int64_t d_start, dse_race *out);
+
+/* The result of the union of two adjacent ranges, by host arithmetic only; out may alias a or b.
+ * Needs a->g_start + a->nbits == b->g_start, equal q, a and b, and b->d_start == a->d_end (else
+ * DSE_EINVAL; out is not touched); a union that ends above 2^62 gives DSE_ERANGE. Counts and the
+ * four step counters add; first_* is a's if a has one, otherwise b's; the maximum keeps the first
+ * strictly greatest and the minimum the first strictly smallest, and a side with steps == 0 takes
+ * no part in either. */
+int32_t dse_race_merge(const dse_race *a, const dse_race *b, dse_race *out);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -530,6 +607,10 @@ int32_t dse_goldbach_merge(const dse_goldbach *a, const dse_goldbach *b, dse_gol
  *   "goldbach_grid" = k in 1..1024: the dse_goldbach_* launches use at most k
  *   workgroups, so one workgroup walks several tiles and the closing launch
  *   sums several slabs on tiny inputs; 0 = default (one resident round).
+ *   "race_grid" = k in 1..1024: the dse_race_* launches use at most k
+ *   workgroups, so one workgroup walks several tiles, a workgroup's D starts
+ *   from the slabs before its own and the closing launch reduces several slabs
+ *   on tiny inputs; 0 = default (one resident round).
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -632,6 +713,13 @@ int32_t dse_debug_query_host(const uint64_t *mask, uint64_t g_start, uint64_t nb
 int32_t dse_debug_goldbach_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits,
                                 const uint64_t *below, uint32_t below_shift, uint64_t below_bits,
                                 uint32_t nprimes, dse_goldbach *out);
+
+/* The dse_race_* kernels' own per-word bodies, run on the host in a plain loop over
+ * the words of a host mask (no device call): the same result as dse_race_dev_async
+ * on the same bits. Test-only; DSE_EINVAL / DSE_ERANGE as dse_race_dev_async for
+ * the pointers, q, a, b, d_start and the range. */
+int32_t dse_debug_race_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, uint32_t q,
+                            uint32_t a, uint32_t b, int64_t d_start, dse_race *out);
 
 /* The wheel kernel's integer helpers, run elementwise on the device by the
  * functions the kernels themselves call: out_dev[i] = op(x_dev[i], y_dev[i])

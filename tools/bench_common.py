@@ -69,3 +69,20 @@ def events(fn, reps):
 
 def ms(ts, nd=1):
     return [round(t * 1e3, nd) for t in ts]
+
+
+class Record:
+    """race_bench.py: print() that also keeps the lines: record.write(path) leaves them in a file (a tool's
+    --out), its directory created."""
+
+    def __init__(self):
+        self.lines = []
+
+    def __call__(self, line: str = ""):
+        print(line, flush=True)
+        self.lines.append(line)
+
+    def write(self, path: str, append: bool = False):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "a" if append else "w") as f:
+            f.write("\n".join(self.lines) + "\n")
