@@ -3,7 +3,7 @@
 // primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
 // dse_stats_host.cpp: statistics of a mask; dse_query_host.cpp: rank and
 // select; dse_goldbach_host.cpp: minimal Goldbach partitions; dse_race_host.cpp: residue classes
-// and races): contexts, device state, the slab
+// and races; dse_tuples_host.cpp: constellations as numbers): contexts, device state, the slab
 // pipe, and the result pass over resident chunks. Not installed; include/dse.h is the ABI.
 #pragma once
 #include <rccl/rccl.h>
@@ -65,9 +65,9 @@ struct DevState {
   Buf counts;                // device scratch (unsigned long long)
   Buf scratch_mask;          // for dse_sieve_chunk
   Scratch scratch;           // bucketed-pass scratch (high-offset ranges)
-  SlabPipe pipe;             // slabs to the host: finish text, prime values
+  SlabPipe pipe;             // slabs to the host: finish text, prime values, constellation values
   StreamScratch finish_sums; // device finish (dse_finish.hip): tile-sum scratch of the three launches
-  StreamScratch primes_sums; // primes as numbers (dse_primes.hip): tile-sum scratch of the three launches
+  StreamScratch primes_sums; // primes and constellations as numbers (dse_primes.hip, dse_tuples.hip): tile-sum scratch of the three launches; dse_tuples_resident's totals and head words
   StreamScratch stats_scratch; // statistics (dse_stats.hip): the workgroups' slabs, and results on their way to the host
   StreamScratch query_scratch; // rank and select (dse_query.hip): queries and answers on their way, dse_query_range's index
   StreamScratch goldbach_scratch; // Goldbach partitions (dse_goldbach.hip): the workgroups' slabs, results on their way to the host, a neighbour chunk's tail
@@ -209,6 +209,29 @@ int32_t slab_send(SlabPipe& p, int s, uint64_t bytes, hipStream_t producer);
 int32_t slab_wait(SlabPipe& p, int s);
 // After an error: leaves nothing in flight on the buffers.
 void slab_drain(SlabPipe& p, hipStream_t producer);
+
+// The slab pipeline of the compactions by rank window (dse_primes_host.cpp), shared by primes as
+// numbers and constellations as numbers. A RankSource is a unit's two launches over a device mask of
+// nbits candidates that is ready in the stream's order:
+//   scan(first, out_cap, totals, tile_sums, stream)              launch_primes_scan's contract,
+//   emit(first, out, out_cap, tile_sums, tile0, tiles, stream)   launch_primes_emit's.
+// rank_pipeline: mask -> out. The scan runs once on d.stream into d.primes_sums; rank_slabs brings
+// the n_out values of ranks [first, first + n_out) of a scanned tile_sums to `out`: the sums are
+// copied to the host, and every slab of at most `slab` ranks (the pipe's buffers, or the test option
+// primes_slab_entries) is emitted over the tiles that hold its ranks (the sums are monotone: two
+// binary searches). Slab i + 1 is emitted on d.stream while slab i's values are copied on the copy
+// stream and slab i - 1 is copied into the caller's memory by this thread. The device is current.
+struct RankSource {
+  uint64_t nbits;
+  std::function<hipError_t(uint64_t, uint64_t, unsigned long long*, void*, hipStream_t)> scan;
+  std::function<hipError_t(uint64_t, uint64_t*, uint64_t, const void*, uint64_t, uint64_t, hipStream_t)> emit;
+};
+// DSE_EINVAL for a null `out` with a capacity (out may be null for a count)
+int32_t rank_check_out(const uint64_t* out, uint64_t out_cap);
+int32_t rank_pipeline(dse_ctx* ctx, DevState& d, const RankSource& src, uint64_t first, uint64_t* out,
+                      uint64_t out_cap, uint64_t* total, uint64_t* written);
+int32_t rank_slabs(dse_ctx* ctx, DevState& d, const RankSource& src, const void* sums, uint64_t first, uint64_t n_out,
+                   uint64_t* out);
 
 }  // namespace dse
 #pragma GCC visibility pop

@@ -1,11 +1,11 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
-// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip, dse_race.hip, and the test-only dse_arith_probe.hip)
+// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip, dse_race.hip, dse_tuples.hip, and the test-only dse_arith_probe.hip)
 // and the C-ABI host layer (dse_host.cpp,
 // dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp, dse_query_host.cpp,
-// dse_goldbach_host.cpp, dse_race_host.cpp). Not installed;
+// dse_goldbach_host.cpp, dse_race_host.cpp, dse_tuples_host.cpp). Not installed;
 // include/dse.h is the ABI. The units that read a resident mask (finish,
-// primes, stats, query, goldbach, race) share its range, tiles and clipped word load (dse_mask.h);
+// primes, stats, query, goldbach, race, tuples) share its range, tiles and clipped word load (dse_mask.h);
 // every unit with a workgroup sum, scan or best-of takes it from dse_block.h; the two that reduce
 // a range to one struct through per-workgroup slabs (stats, goldbach, race) share dse_slab.h.
 #pragma once
@@ -262,6 +262,27 @@ hipError_t launch_primes_scan(uint64_t g_start, uint64_t nbits, const uint64_t* 
 hipError_t launch_primes_emit(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t first, uint64_t* out,
                               uint64_t out_cap, const void* tile_sums, uint64_t tile0, uint64_t tiles,
                               hipStream_t stream);
+// The scan launch alone, on ntiles tile counts at tile_sums (ntiles + 1 uint64): what
+// launch_primes_scan ends with, and the scan of every other compaction by rank window.
+hipError_t launch_rank_scan(void* tile_sums, uint64_t ntiles, uint64_t first, uint64_t out_cap,
+                            unsigned long long* totals, hipStream_t stream);
+
+// Constellations as numbers (dse_tuples.hip): the positions of mask (odd indices [g_start,
+// g_start + nbits)) at which the pattern (require, forbid) matches (dse_tuples_word.h), as uint64
+// values 3 + 2 (g_start + position), ranked in increasing order. The above_bits <= 31 candidates
+// behind the range are the bits of `above` from bit above_shift on. The launches, the scratch
+// (primes_scratch_bytes(nbits)) and the totals are launch_primes_scan's and launch_primes_emit's.
+struct TuplePattern {
+  uint32_t require, forbid;
+  const uint64_t* above;
+  uint32_t above_shift, above_bits;
+};
+hipError_t launch_tuples_scan(uint64_t g_start, uint64_t nbits, const uint64_t* mask, const TuplePattern& p,
+                              uint64_t first, uint64_t out_cap, unsigned long long* totals, void* tile_sums,
+                              hipStream_t stream);
+hipError_t launch_tuples_emit(uint64_t g_start, uint64_t nbits, const uint64_t* mask, const TuplePattern& p,
+                              uint64_t first, uint64_t* out, uint64_t out_cap, const void* tile_sums, uint64_t tile0,
+                              uint64_t tiles, hipStream_t stream);
 
 // Statistics of a mask (dse_stats.hip): the two launches of a slab reduction (dse_slab.h), which
 // write the dse_stats (kStatsWords uint64 words) at `stats`. grid = stats_grid(nbits, CUs of the

@@ -2,8 +2,8 @@
 // that turns a device-resident mask into something else: the device finish
 // (dse_finish.hip), primes as numbers (dse_primes.hip), the statistics
 // (dse_stats.hip), rank and select (dse_query.hip), the Goldbach partitions
-// (dse_goldbach.hip), the residue classes and races (dse_race.hip) and their
-// host sides.
+// (dse_goldbach.hip), the residue classes and races (dse_race.hip), the constellations as numbers
+// (dse_tuples.hip) and their host sides.
 //
 // A range is the odd indices [g_start, g_start + nbits), one bit each, in
 // `words` 64-bit words; the kernels walk it in tiles of kMaskTileWords words,

@@ -99,6 +99,10 @@ SIGNATURES = {
     "dse_race_range": (_i32, [_vp, _u64, _u64, _u32, _u32, _u32, _i64, _pu64]),
     "dse_race_resident": (_i32, [_vp, _i32, _u32, _u32, _u32, _i64, _pu64]),
     "dse_race_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_tuples_dev_async": (_i32, [_vp, _u64, _u64, _vp, _u32, _u32, _vp, _u32, _u32, _u64, _vp, _u64, _vp, _vp]),
+    "dse_tuples_range": (_i32, [_vp, _u64, _u64, _u32, _u32, _u64, _pu64, _u64, _pu64, _pu64]),
+    "dse_tuples_resident": (_i32, [_vp, _i32, _u32, _u32, _u64, _pu64, _u64, _pu64, _pu64]),
+    "dse_debug_tuples_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _pu64, _u32, _u32, _u64, _pu64, _u64, _pu64]),
     "dse_debug_race_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _u32, _i64, _pu64]),
     "dse_debug_goldbach_host": (_i32, [_pu64, _u64, _u64, _pu64, _u32, _u64, _u32, _pu64]),
     "dse_debug_query_host": (_i32, [_pu64, _u64, _u64, _u32, _pu64, _u64, _pu64]),

@@ -48,6 +48,44 @@ SEXTUPLETS = pattern(0, 4, 6, 10, 12, 16)
 CONSTELLATIONS = (TWINS,) + TRIPLETS + (QUADRUPLETS,) + QUINTUPLETS + (SEXTUPLETS,)
 
 
+def exact_gap(d: int):
+    """(require, forbid) of the consecutive primes exactly 2d apart (include/dse.h
+    "constellations as numbers"): p and p + 2d prime, nothing prime between them."""
+    if d < 1 or d > 31:
+        raise ValueError("d is in 1..31")
+    return 1 | 1 << d, (1 << d) - 2
+
+
+def tuple_members(values, require: int) -> np.ndarray:
+    """The (n, k) uint64 array of all members of the matches whose lowest members
+    are ``values``: column c is values + 2j for the c-th set bit j of require."""
+    offs = np.array([2 * j for j in range(32) if (int(require) >> j) & 1], dtype=np.uint64)
+    v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 1)
+    return v + offs.reshape(1, -1)
+
+
+def tuples_host(mask: np.ndarray, g_start: int, nbits: int, require: int, forbid: int = 0,
+                above: Optional[np.ndarray] = None, above_shift: int = 0, above_bits: int = 0, first: int = 0,
+                count: Optional[int] = None):
+    """Test-only: the tuples kernels' per-word body run on the host over a host mask
+    and a host ``above`` (include/dse.h dse_debug_tuples_host). -> (values, total):
+    the matches of ranks [first, first + count) (count=None: every one from `first` on)."""
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    a = None if above is None else np.ascontiguousarray(above, dtype=np.uint64)
+    tot = np.zeros(2, dtype=np.uint64)
+
+    def call(out, cap):
+        check(lib().dse_debug_tuples_host(u64p(m) if len(m) else None, g_start, nbits, require, forbid,
+                                          u64p(a) if a is not None and len(a) else None, above_shift, above_bits,
+                                          first, out, cap, u64p(tot)), "dse_debug_tuples_host")
+    if count is None:
+        call(None, 0)
+        count = max(0, int(tot[0]) - first)
+    out = np.empty(count, dtype=np.uint64)
+    call(u64p(out) if count else None, count)
+    return out[:int(tot[1])], int(tot[0])
+
+
 def _patterns(patterns):
     """-> (ctypes uint32 array or None, count)"""
     pats = [int(p) for p in patterns]
@@ -496,6 +534,50 @@ class Context:
             return self.stats_range(min((a - 3) // 2, 1 << 62), 0, patterns)
         b = hi if hi & 1 else hi - 1
         return self.stats_range((a - 3) // 2, (b - a) // 2 + 1, patterns)
+
+    # -- constellations as numbers -------------------------------------------------
+    def tuples_dev_async(self, g_start: int, nbits: int, mask_ptr: int, require: int, forbid: int, above_ptr: int,
+                         above_shift: int, above_bits: int, first: int, out_ptr: int, out_cap: int, totals_ptr: int,
+                         stream_ptr: int = 0):
+        """The positions of the device mask at which (require, forbid) matches, as
+        uint64 values 3 + 2 (g_start + position) in device memory; the above_bits
+        candidates behind the range are the bits from above_shift on of the device
+        bit string at above_ptr (include/dse.h dse_tuples_dev_async): out[i] = the
+        match of rank first + i; totals[0] = matches of the range, totals[1] = written."""
+        check(lib().dse_tuples_dev_async(self.ptr, g_start, nbits, mask_ptr or None, require, forbid,
+                                         above_ptr or None, above_shift, above_bits, first, out_ptr or None, out_cap,
+                                         totals_ptr, stream_ptr or None),
+              "dse_tuples_dev_async")
+
+    def tuples_range(self, g_start: int, nbits: int, require: int, forbid: int = 0, first: int = 0,
+                     count: Optional[int] = None) -> np.ndarray:
+        """gen-table + sieve-e of an odd-index range (and of the 31 candidates above
+        it) and the lowest members of its matches of (require, forbid), extracted
+        on the device: ranks [first, first + count) (count=None: all from `first`)."""
+        L = lib()
+        return self._primes("dse_tuples_range",
+                            lambda f, o, c, t, w: L.dse_tuples_range(self.ptr, g_start, nbits, require, forbid,
+                                                                     f, o, c, t, w),
+                            first, count)
+
+    def resident_tuples(self, require: int, forbid: int = 0, my_num: Optional[int] = None, first: int = 0,
+                        count: Optional[int] = None) -> np.ndarray:
+        """The same for a chunk the last sieve_all left on its device (it sees the
+        head of the chunk after it), or (my_num=None) for all its chunks as one range."""
+        L = lib()
+        k = 0 if my_num is None else my_num
+        return self._primes("dse_tuples_resident",
+                            lambda f, o, c, t, w: L.dse_tuples_resident(self.ptr, k, require, forbid, f, o, c, t, w),
+                            first, count)
+
+    def tuples_window(self, lo: int, hi: int, require: int, forbid: int = 0) -> np.ndarray:
+        """The matches whose lowest member lies in the odd values of [max(lo, 3), hi]
+        (primes_window's convention); the other members may lie above hi."""
+        a = max(lo, 3) | 1
+        if hi < a:
+            return np.empty(0, dtype=np.uint64)
+        b = hi if hi & 1 else hi - 1
+        return self.tuples_range((a - 3) // 2, (b - a) // 2 + 1, require, forbid)
 
 
     # -- additive questions -------------------------------------------------------

@@ -560,6 +560,69 @@ int32_t dse_race_resident(dse_ctx *ctx, int32_t my_num, uint32_t q, uint32_t a, 
  * no part in either. */
 int32_t dse_race_merge(const dse_race *a, const dse_race *b, dse_race *out);
 
+/* ---- constellations as numbers ----------------------------------------------- */
+
+/* Where the matches of a pattern are: the positions of a device-resident mask at which a pattern
+ * matches, as little-endian uint64 values, in increasing order, extracted on the GPU. The counting
+ * half is dse_stats' matches[] and gaps[].
+ *
+ * Pattern. Two uint32: `require`, with bit 0 set as a dse_stats pattern has, and `forbid`, with
+ * require & forbid == 0. Bit j of require: the candidate j places above must be an entry; bit j of
+ * forbid: it must not be. The span is the bit length of require | forbid (<= 32). forbid = 0 gives
+ * exactly the dse_stats patterns; require = 1 | 1 << d with forbid = the bits 1 .. d - 1 lists the
+ * consecutive primes exactly 2d apart, d <= 31.
+ *
+ * Visible candidates. The range's own nbits candidates, followed by above_bits <= 31 candidates of
+ * the caller's: the bits of the bit string at `above` from bit above_shift < 64 on (the way
+ * dse_goldbach_dev_async takes `below`). `above` is 8-byte aligned, may be NULL when above_bits == 0
+ * and may point into a larger mask: only the whole words that cover the bits are read.
+ *
+ * Match. Position i < nbits matches when i + span <= nbits + above_bits, every required candidate is
+ * a visible entry and every forbidden one is visible and not an entry. A match belongs to the range
+ * that holds its lowest member, so adjacent ranges that each see the next one's head as `above` list
+ * every match of their union exactly once, in order. With forbid = 0 and above_bits = 0 this is
+ * dse_stats' rule "all members inside the range".
+ *
+ * Output. The matches are ranked 0, 1, ... in increasing position; the value of a match is
+ * 3 + 2 (g_start + i), its lowest member. A call returns the rank window [first, first + out_cap)
+ * as dse_primes_* do, so a count costs no output. */
+
+/* Async on stream. totals_dev[0] = matches of the range (always written); totals_dev[1] = elements
+ * written = min(out_cap, max(0, matches - first)); out_dev[i] = value of the match of rank
+ * first + i. Nothing outside [out_dev, out_dev + totals_dev[1]) is touched; out_dev may be NULL when
+ * out_cap == 0 (count only) and must be 8-byte aligned. Bits past nbits in the last mask word are
+ * ignored; nbits = 0 writes totals 0, 0. DSE_EINVAL for a null ctx or totals, a null mask with
+ * nbits > 0, a null out_dev with out_cap > 0, a misaligned out_dev, require with bit 0 clear,
+ * require & forbid != 0, above_bits > 31, above_shift > 63, or a null or misaligned above_dev with
+ * above_bits > 0. DSE_ERANGE for visible candidates beyond 2^62 or more than 2^44 candidates in
+ * one call. */
+int32_t dse_tuples_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                             const uint64_t *mask_dev, uint32_t require, uint32_t forbid,
+                             const uint64_t *above_dev, uint32_t above_shift, uint32_t above_bits,
+                             uint64_t first, uint64_t *out_dev, uint64_t out_cap,
+                             uint64_t *totals_dev, void *stream);
+
+/* gen-table + sieve-e + the matches of an odd-index range, on the first device; host buffer. The
+ * range is sieved together with the candidates above it in one scratch mask (31 of them, fewer where
+ * the 2^62 bound ends them), which are its `above`. *total = matches of the range, *written = values
+ * stored to out (either may be NULL); the values cross to the host through dse_primes_range's slab
+ * pipeline. */
+int32_t dse_tuples_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, uint32_t require,
+                         uint32_t forbid, uint64_t first, uint64_t *out, uint64_t out_cap,
+                         uint64_t *total, uint64_t *written);
+
+/* The same for chunk my_num left resident by the last dse_sieve_all; my_num = 0: for all P chunks
+ * as the one range [3, 3 + 2 P cs) (dse_stats_resident's convention). Chunk k < P sees the first 31
+ * candidates of chunk k + 1 (a pointer into that mask when both are on one device, otherwise that
+ * one word copied); chunk P has no `above`: the dropped tail is in no mask. Every chunk's size and
+ * scan launches are enqueued on its device's stream before any is waited for; the host forms the
+ * running totals, cuts the rank window per chunk, and each chunk's slice goes through the slab
+ * pipeline to its offset in out. DSE_EINVAL if the chunk is not resident, or for chunks of fewer
+ * than 31 candidates when a chunk with a successor is asked for. */
+int32_t dse_tuples_resident(dse_ctx *ctx, int32_t my_num, uint32_t require, uint32_t forbid,
+                            uint64_t first, uint64_t *out, uint64_t out_cap, uint64_t *total,
+                            uint64_t *written);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -720,6 +783,16 @@ int32_t dse_debug_goldbach_host(const uint64_t *mask, uint64_t g_start, uint64_t
  * the pointers, q, a, b, d_start and the range. */
 int32_t dse_debug_race_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, uint32_t q,
                             uint32_t a, uint32_t b, int64_t d_start, dse_race *out);
+
+/* The dse_tuples_* kernels' own per-word body, run on the host in a plain loop over
+ * the words of a host mask and a host `above` (no device call): the same totals and
+ * values as dse_tuples_dev_async on the same bits. Test-only; DSE_EINVAL /
+ * DSE_ERANGE as dse_tuples_dev_async for the pointers, the pattern, `above` and the
+ * range. */
+int32_t dse_debug_tuples_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits,
+                              uint32_t require, uint32_t forbid, const uint64_t *above,
+                              uint32_t above_shift, uint32_t above_bits, uint64_t first,
+                              uint64_t *out, uint64_t out_cap, uint64_t totals[2]);
 
 /* The wheel kernel's integer helpers, run elementwise on the device by the
  * functions the kernels themselves call: out_dev[i] = op(x_dev[i], y_dev[i])

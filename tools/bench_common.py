@@ -1,4 +1,4 @@
-"""What finish_bench.py, primes_bench.py, stats_bench.py, query_bench.py and goldbach_bench.py share: the package on sys.path, the
+"""What finish_bench.py, primes_bench.py, stats_bench.py, query_bench.py, goldbach_bench.py, race_bench.py and tuples_bench.py share: the package on sys.path, the
 DSE_LIB override (A/B another build of the library, as bench.py does), a per-step time limit and
 the two timers (host clock and HIP events), each the median of `reps` runs after one warm-up."""
 from __future__ import annotations
