@@ -3,7 +3,7 @@
 // primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
 // dse_stats_host.cpp: statistics of a mask; dse_query_host.cpp: rank and
 // select; dse_goldbach_host.cpp: minimal Goldbach partitions; dse_race_host.cpp: residue classes
-// and races; dse_tuples_host.cpp: constellations as numbers): contexts, device state, the slab
+// and races; dse_tuples_host.cpp: constellations as numbers; dse_gaps_host.cpp: where the gaps are): contexts, device state, the slab
 // pipe, and the result pass over resident chunks. Not installed; include/dse.h is the ABI.
 #pragma once
 #include <rccl/rccl.h>
@@ -72,6 +72,7 @@ struct DevState {
   StreamScratch query_scratch; // rank and select (dse_query.hip): queries and answers on their way, dse_query_range's index
   StreamScratch goldbach_scratch; // Goldbach partitions (dse_goldbach.hip): the workgroups' slabs, results on their way to the host, a neighbour chunk's tail
   StreamScratch race_scratch; // residue classes and races (dse_race.hip): the workgroups' slabs, results on their way to the host
+  StreamScratch gaps_scratch; // where the gaps are (dse_gaps.hip): the workgroups' slabs, results on their way to the host
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
 };
 
@@ -109,6 +110,7 @@ struct dse_ctx {
   uint32_t query_grid = 0;  // test-only: > 0 caps the workgroups of a query launch
   uint32_t goldbach_grid = 0;  // test-only: > 0 caps the workgroups of a Goldbach launch
   uint32_t race_grid = 0;  // test-only: > 0 caps the workgroups of a race launch
+  uint32_t gaps_grid = 0;  // test-only: > 0 caps the workgroups of a gaps launch
   int64_t query_index_builds = 0;  // rank indices built for resident chunks (dse_debug_get_stat)
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:

@@ -336,4 +336,15 @@ uint64_t race_scratch_bytes(uint32_t grid);
 hipError_t launch_race(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint32_t q, uint32_t a, uint32_t b,
                        int64_t d_start, uint64_t* out, void* slabs, uint32_t grid, hipStream_t stream);
 
+// Where the prime gaps of a mask are (dse_gaps.hip): the two launches of a slab reduction
+// (dse_slab.h), which write the dse_gaps (kGapsWords uint64 words) at `out`. grid = gaps_grid(nbits,
+// CUs of the device, cap or 0): slab_grid's rule. slabs: gaps_scratch_bytes(grid) bytes of device
+// scratch.
+constexpr uint32_t kGapsMaxGrid = 1024;
+constexpr uint32_t kGapsWords = 9 + 1024;
+uint32_t gaps_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
+uint64_t gaps_scratch_bytes(uint32_t grid);
+hipError_t launch_gaps(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t* out, void* slabs,
+                       uint32_t grid, hipStream_t stream);
+
 }  // namespace dse

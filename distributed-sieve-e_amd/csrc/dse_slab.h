@@ -1,10 +1,10 @@
 // dse_slab.h -- the two-launch slab reduction of the units that turn a whole mask
-// range into one small struct (dse_stats.hip, dse_goldbach.hip; dse_race.hip puts a
+// range into one small struct (dse_stats.hip, dse_goldbach.hip, dse_gaps.hip; dse_race.hip puts a
 // count launch over the same runs in front). Main launch: `grid`
 // workgroups, each walking its own contiguous run of tiles (dse_mask.h) and ending
 // with one slab of plain stores: scalars of the unit's own, the number of histogram
 // bins it filled (word kSlBins) and those bins (from word kSlHist). Closing launch:
-// one workgroup per kSlabCloseBins bins sums them over the slabs; workgroup 0 also
+// one workgroup per kSlabCloseBins bins sums them over the slabs (dse_gaps.hip: takes their minimum); workgroup 0 also
 // reduces the scalars, one slab per thread. The launches are the only ordering.
 // Slab and result layouts and the per-word bodies stay with each unit; so do the
 // main kernels' flush of their register counters and slab stores, which a helper
@@ -66,6 +66,20 @@ __device__ __forceinline__ void slab_sum_bins(const unsigned long long* slabs, u
     if (bin < sl[kSlBins]) acc += sl[kSlHist + bin];
   }
   if (acc) atomicAdd(&s_bins[lane], (unsigned long long)acc);
+}
+
+// The column minimum of a unit whose bins hold positions (~0: none), into s_bins[0 .. kSlabCloseBins),
+// which the caller fills with ~0 and fences with barriers of its own: slab_sum_bins' walk.
+template <uint32_t kSlabWords, uint32_t kSlBins, uint32_t kSlHist>
+__device__ __forceinline__ void slab_min_bins(const unsigned long long* slabs, uint32_t nslabs,
+                                              unsigned long long* s_bins) {
+  const uint32_t grp = threadIdx.x >> 6, lane = threadIdx.x & 63u, bin = blockIdx.x * kSlabCloseBins + lane;
+  uint64_t acc = ~0ull;
+  for (uint32_t s = grp; s < nslabs; s += kSlabCloseThreads / 64) {
+    const unsigned long long* const sl = slabs + (uint64_t)s * kSlabWords;
+    if (bin < sl[kSlBins]) acc = min(acc, (uint64_t)sl[kSlHist + bin]);
+  }
+  if (acc != ~0ull) atomicMin(&s_bins[lane], (unsigned long long)acc);
 }
 
 // the main launch unless the range is empty, then the closing launch over `bins` histogram bins

@@ -37,6 +37,9 @@ GOLDBACH_PRIMES, GOLDBACH_WORDS, GOLDBACH_NONE = 2048, 8 + 2048, (1 << 64) - 1
 # include/dse.h dse_race as uint64 words: 17 scalar members, then counts[64]
 RACE_MAX_MODULUS, RACE_WORDS, RACE_NONE = 64, 17 + 64, (1 << 64) - 1
 
+# include/dse.h dse_gaps as uint64 words: 9 scalar members, then first[1024]
+GAPS_BINS, GAPS_WORDS, GAPS_NONE = 1024, 9 + 1024, (1 << 64) - 1
+
 # include/dse.h DSE_QUERY_*
 QUERY_NONE = (1 << 64) - 1
 QUERY_RANK, QUERY_SELECT, QUERY_NEXT, QUERY_PREV, QUERY_TEST = range(5)
@@ -102,6 +105,12 @@ SIGNATURES = {
     "dse_tuples_dev_async": (_i32, [_vp, _u64, _u64, _vp, _u32, _u32, _vp, _u32, _u32, _u64, _vp, _u64, _vp, _vp]),
     "dse_tuples_range": (_i32, [_vp, _u64, _u64, _u32, _u32, _u64, _pu64, _u64, _pu64, _pu64]),
     "dse_tuples_resident": (_i32, [_vp, _i32, _u32, _u32, _u64, _pu64, _u64, _pu64, _pu64]),
+    "dse_gaps_dev_async": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "dse_gaps_range": (_i32, [_vp, _u64, _u64, _pu64]),
+    "dse_gaps_resident": (_i32, [_vp, _i32, _pu64]),
+    "dse_gaps_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_gaps_records": (_i32, [_pu64, _pu32, _u32, _pu32]),
+    "dse_debug_gaps_host": (_i32, [_pu64, _u64, _u64, _pu64]),
     "dse_debug_tuples_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _pu64, _u32, _u32, _u64, _pu64, _u64, _pu64]),
     "dse_debug_race_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _u32, _i64, _pu64]),
     "dse_debug_goldbach_host": (_i32, [_pu64, _u64, _u64, _pu64, _u32, _u64, _u32, _pu64]),

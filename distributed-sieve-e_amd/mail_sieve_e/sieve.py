@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -169,6 +169,81 @@ def stats_host(mask: np.ndarray, g_start: int, nbits: int, patterns=CONSTELLATIO
     check(lib().dse_debug_stats_host(u64p(m) if len(m) else None, g_start, nbits, pats, n, u64p(out)),
           "dse_debug_stats_host")
     return Stats(out)
+
+
+class Gaps:
+    """One dse_gaps (include/dse.h "where the gaps are"): the first occurrence of
+    every prime gap of the odd candidates [g_start, g_start + nbits). ``words`` is
+    the struct as its uint64 words."""
+
+    def __init__(self, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.shape != (_dse.GAPS_WORDS,):
+            raise ValueError("a dse_gaps is %d uint64 words" % _dse.GAPS_WORDS)
+        self.words = w
+
+    @staticmethod
+    def _opt(v):
+        return None if v == _dse.GAPS_NONE else v
+
+    g_start = property(lambda s: int(s.words[0]))
+    nbits = property(lambda s: int(s.words[1]))
+    primes = property(lambda s: int(s.words[2]))
+    first_g = property(lambda s: Gaps._opt(int(s.words[3])))
+    last_g = property(lambda s: Gaps._opt(int(s.words[4])))
+    found = property(lambda s: int(s.words[5]))
+    max_gap = property(lambda s: int(s.words[6]))
+    max_gap_g = property(lambda s: Gaps._opt(int(s.words[7])))
+    overflow_g = property(lambda s: Gaps._opt(int(s.words[8])))
+
+    @property
+    def first(self) -> np.ndarray:
+        """uint64[1024]: first[d] = g of the lower prime of the first gap equal to 2d,
+        _dse.GAPS_NONE where the range has none."""
+        return self.words[9:9 + _dse.GAPS_BINS]
+
+    @property
+    def max_gap_prime(self) -> Optional[int]:
+        """The lower prime of the first maximal gap, or None with fewer than two primes."""
+        return None if self.max_gap_g is None else 3 + 2 * self.max_gap_g
+
+    def _pairs(self, ds) -> List[Tuple[int, int]]:
+        f = self.first
+        return [(2 * int(d), 3 + 2 * int(f[int(d)])) for d in ds]
+
+    def first_primes(self) -> List[Tuple[int, int]]:
+        """(gap value 2d, lower prime of its first occurrence) for the found bins, by gap."""
+        return self._pairs(np.flatnonzero(self.first != np.uint64(_dse.GAPS_NONE)))
+
+    def records(self) -> List[Tuple[int, int]]:
+        """The same pairs for the maximal gaps of the range (dse_gaps_records): the gaps
+        that no longer gap precedes."""
+        n = ctypes.c_uint32(0)
+        d = (ctypes.c_uint32 * _dse.GAPS_BINS)()
+        check(lib().dse_gaps_records(u64p(self.words), d, _dse.GAPS_BINS, ctypes.byref(n)), "dse_gaps_records")
+        return self._pairs(d[:n.value])
+
+    def merge(self, other: "Gaps") -> "Gaps":
+        """The table of this range followed by the adjacent ``other`` (dse_gaps_merge)."""
+        out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
+        check(lib().dse_gaps_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_gaps_merge")
+        return Gaps(out)
+
+    def __eq__(self, other):
+        return isinstance(other, Gaps) and np.array_equal(self.words, other.words)
+
+    def __repr__(self):
+        return (f"Gaps(g_start={self.g_start}, nbits={self.nbits}, primes={self.primes}, found={self.found}, "
+                f"max_gap={self.max_gap} at {self.max_gap_prime})")
+
+
+def gaps_host(mask: np.ndarray, g_start: int, nbits: int) -> Gaps:
+    """Test-only: the gaps kernels' per-word bodies run on the host over a host mask
+    (include/dse.h dse_debug_gaps_host)."""
+    out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    check(lib().dse_debug_gaps_host(u64p(m) if len(m) else None, g_start, nbits, u64p(out)), "dse_debug_gaps_host")
+    return Gaps(out)
 
 
 class Goldbach:
@@ -534,6 +609,38 @@ class Context:
             return self.stats_range(min((a - 3) // 2, 1 << 62), 0, patterns)
         b = hi if hi & 1 else hi - 1
         return self.stats_range((a - 3) // 2, (b - a) // 2 + 1, patterns)
+
+    # -- where the gaps are -----------------------------------------------------------
+    def gaps_dev_async(self, g_start: int, nbits: int, mask_ptr: int, out_ptr: int, stream_ptr: int = 0):
+        """The first occurrence of every gap of the device mask as one dse_gaps
+        (_dse.GAPS_WORDS uint64 words) in device memory at out_ptr (include/dse.h
+        dse_gaps_dev_async)."""
+        check(lib().dse_gaps_dev_async(self.ptr, g_start, nbits, mask_ptr or None, out_ptr or None,
+                                       stream_ptr or None),
+              "dse_gaps_dev_async")
+
+    def gaps_range(self, g_start: int, nbits: int) -> Gaps:
+        """gen-table + sieve-e of an odd-index range and the first occurrence of every
+        gap in it, computed on the device: only the dse_gaps reaches the host."""
+        out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
+        check(lib().dse_gaps_range(self.ptr, g_start, nbits, u64p(out)), "dse_gaps_range")
+        return Gaps(out)
+
+    def resident_gaps(self, my_num: Optional[int] = None) -> Gaps:
+        """The table of a chunk the last sieve_all left on its device, or (my_num=None)
+        of all its chunks: the per-chunk results merged in order."""
+        out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
+        check(lib().dse_gaps_resident(self.ptr, 0 if my_num is None else my_num, u64p(out)), "dse_gaps_resident")
+        return Gaps(out)
+
+    def gaps_window(self, lo: int, hi: int) -> Gaps:
+        """The table of the odd values in [max(lo, 3), hi] (primes_window's convention);
+        an empty window gives the empty result."""
+        a = max(lo, 3) | 1
+        if hi < a:
+            return self.gaps_range(min((a - 3) // 2, 1 << 62), 0)
+        b = hi if hi & 1 else hi - 1
+        return self.gaps_range((a - 3) // 2, (b - a) // 2 + 1)
 
     # -- constellations as numbers -------------------------------------------------
     def tuples_dev_async(self, g_start: int, nbits: int, mask_ptr: int, require: int, forbid: int, above_ptr: int,

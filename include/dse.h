@@ -623,6 +623,74 @@ int32_t dse_tuples_resident(dse_ctx *ctx, int32_t my_num, uint32_t require, uint
                             uint64_t first, uint64_t *out, uint64_t out_cap, uint64_t *total,
                             uint64_t *written);
 
+/* ---- where the gaps are ----------------------------------------------------- */
+
+/* The first occurrence of every prime gap of a device-resident mask (A000230) and, from it, the
+ * maximal or record gaps (A002386, A005250), computed on the GPU in one read of the mask; only the
+ * dse_gaps crosses to the host. Candidates, entries, values and g are dse_stats': candidate g is the
+ * value 3 + 2g, an entry is a set bit. A gap is the difference of two consecutive entries that both
+ * lie in the range: it has d places (the difference of the candidate indices) and the value 2d, and
+ * its position is the global candidate index g of its lower prime. The prime 2 is in no mask and the
+ * gap 2 -> 3 is never seen.
+ *
+ * first[d] = position of the first gap of exactly d places, d < DSE_GAPS_BINS, DSE_GAPS_NONE where
+ * the range has none; first[0] is always DSE_GAPS_NONE. found counts the bins that are not NONE.
+ * Gaps of DSE_GAPS_BINS places and more (synthetic masks only: every prime gap below 2^64 is under
+ * 1600) have one bin, overflow_g, the position of the first of them. max_gap and max_gap_g are
+ * exactly dse_stats' members: max_gap is exact whatever its size, max_gap_g the position of the
+ * FIRST such gap; with fewer than two primes max_gap = 0 and max_gap_g = DSE_GAPS_NONE.
+ *
+ * Every member is a uint64_t and there is no padding: bindings may treat a dse_gaps as an array of
+ * DSE_GAPS_WORDS uint64 words. */
+#define DSE_GAPS_BINS 1024
+#define DSE_GAPS_NONE UINT64_MAX
+#define DSE_GAPS_WORDS (9 + DSE_GAPS_BINS)
+typedef struct dse_gaps {
+  uint64_t g_start, nbits;     /* the range the numbers are of */
+  uint64_t primes;             /* set bits */
+  uint64_t first_g, last_g;    /* first / last entry, DSE_GAPS_NONE if none */
+  uint64_t found;              /* bins d < DSE_GAPS_BINS with first[d] != NONE */
+  uint64_t max_gap, max_gap_g; /* exactly dse_stats' members: 2d of the longest gap, g of the FIRST such; 0 / NONE */
+  uint64_t overflow_g;         /* g of the first gap of >= DSE_GAPS_BINS places (synthetic masks only), NONE */
+  uint64_t first[DSE_GAPS_BINS]; /* first[d] = g of the lower prime of the first gap of exactly d places; NONE if there is none; first[0] is always NONE */
+} dse_gaps;
+
+/* Async on stream, on a caller-owned device mask. out_dev: sizeof(dse_gaps) bytes of device memory,
+ * 8-byte aligned; every member is written and nothing outside it is touched. Bits past nbits in the
+ * last word are ignored; nbits = 0 writes the empty result. DSE_EINVAL for a null ctx or out_dev, a
+ * null mask with nbits > 0 or a misaligned out_dev. DSE_ERANGE for a range beyond 2^62 or more than
+ * 2^44 candidates in one call. */
+int32_t dse_gaps_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                           const uint64_t *mask_dev, dse_gaps *out_dev, void *stream);
+
+/* gen-table + sieve-e + the table of an odd-index range, on the first device; host result. The
+ * range rules of dse_sieve_odd_range apply. */
+int32_t dse_gaps_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, dse_gaps *out);
+
+/* The table of chunk my_num left resident by the last dse_sieve_all; my_num = 0: of all P chunks,
+ * that is of [3, 3 + 2 P cs) (dse_stats_resident's convention). For all chunks, every chunk's
+ * launches are enqueued on its own device's stream before any is waited for, and the P results are
+ * merged on the host in chunk order: the merge rebuilds a seam's gap from the two sides' last and
+ * first entry, so no chunk sees its neighbour. DSE_EINVAL if the chunk is not resident. */
+int32_t dse_gaps_resident(dse_ctx *ctx, int32_t my_num, dse_gaps *out);
+
+/* The table of the union of two adjacent ranges, by host arithmetic only; out may alias a or b.
+ * Needs a->g_start + a->nbits == b->g_start (else DSE_EINVAL; out is not touched); a union that ends
+ * above 2^62 gives DSE_ERANGE. primes adds; first_g / last_g come from whichever side has them. With
+ * an entry on both sides the seam's gap has s = b->first_g - a->last_g places at position a->last_g,
+ * which lies above every position of a and below every one of b: first[d] is a's if set, else the
+ * seam's if d == s, else b's; overflow_g is decided the same way, the seam counting when s >=
+ * DSE_GAPS_BINS. The maximal gap is taken over a, the seam, then b, keeping the first strictly
+ * greatest; found is recounted. The merge is associative, with empty and prime-less pieces on
+ * either side. */
+int32_t dse_gaps_merge(const dse_gaps *a, const dse_gaps *b, dse_gaps *out);
+
+/* The maximal gaps of the range, by host arithmetic: bin d (1 <= d < DSE_GAPS_BINS) is a record when
+ * first[d] != NONE and no longer gap starts lower, in a higher bin or at overflow_g. *count = their
+ * number; their d go to d_out in increasing order, up to cap of them. d_out may be NULL with cap = 0.
+ * DSE_EINVAL for a null g or count, or a null d_out with cap > 0. */
+int32_t dse_gaps_records(const dse_gaps *g, uint32_t *d_out, uint32_t cap, uint32_t *count);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -674,6 +742,9 @@ int32_t dse_tuples_resident(dse_ctx *ctx, int32_t my_num, uint32_t require, uint
  *   workgroups, so one workgroup walks several tiles, a workgroup's D starts
  *   from the slabs before its own and the closing launch reduces several slabs
  *   on tiny inputs; 0 = default (one resident round).
+ *   "gaps_grid" = k in 1..1024: the dse_gaps_* launches use at most k
+ *   workgroups, so one workgroup walks several tiles and the closing launch
+ *   reduces several slabs on tiny inputs; 0 = default (one resident round).
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -685,6 +756,7 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   of broadcast (one per device and call);
  *   "primes_tile_bits": candidates per tile of the dse_primes_* kernels;
  *   "stats_tile_bits": candidates per tile of the dse_stats_* kernels;
+ *   "gaps_tile_bits": candidates per tile of the dse_gaps_* main kernel;
  *   "query_index_builds": rank indices dse_query_resident has built for
  *   resident chunks so far (one per chunk and dse_sieve_all that replaced the
  *   masks);
@@ -783,6 +855,13 @@ int32_t dse_debug_goldbach_host(const uint64_t *mask, uint64_t g_start, uint64_t
  * the pointers, q, a, b, d_start and the range. */
 int32_t dse_debug_race_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, uint32_t q,
                             uint32_t a, uint32_t b, int64_t d_start, dse_race *out);
+
+/* The dse_gaps_* kernels' own per-word bodies, run on the host in a plain loop over
+ * the tiles and words of a host mask (no device call), the settled bins refreshed
+ * per tile as the main kernel does: the same result as dse_gaps_dev_async on the
+ * same bits. Test-only; DSE_EINVAL / DSE_ERANGE as dse_gaps_dev_async for the
+ * pointers and the range. */
+int32_t dse_debug_gaps_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, dse_gaps *out);
 
 /* The dse_tuples_* kernels' own per-word body, run on the host in a plain loop over
  * the words of a host mask and a host `above` (no device call): the same totals and
