@@ -71,7 +71,15 @@ constexpr uint32_t TB1 = DSE_TB1;           // B1/B2 threshold
 #endif
 constexpr uint32_t TB = DSE_TB;             // B2/L threshold
 static_assert(TA <= 256 && TA < TB1 && TB1 <= TB && TB <= KP / 8, "unit thresholds");
-static_assert(KP / (128 * (TA + 1)) <= 10 && KP / (32 * (TB1 + 1)) <= 10, "class_marks_k covers K <= 10");
+// Marks per hit class (class_marks_k). B1 and B2 mark every class to the
+// segment end: a prime p has its hits at indices n <= floor((KP - 1) / p), and
+// a B1 class holds every 128th, so T = floor(floor((KP - 1) / pmin) / 128) + 1
+// <= floor((KP - 1) / (128 (TA + 1))) + 1 marks reach them all (pmin > TA: 11
+// at p = 97 with KP = 2^17, 6 with 2^16); a B2 class holds every 64th, pmin >
+// TB1 (4 and 2 at p = 641).
+constexpr uint32_t kClassMarksMax = 11;
+static_assert((KP - 1) / (128 * (TA + 1)) + 1 <= kClassMarksMax && (KP - 1) / (64 * (TB1 + 1)) + 1 <= kClassMarksMax,
+              "class_marks_k covers K <= kClassMarksMax");
 constexpr uint32_t kMidCap = TB >= 16384 ? 1920 : TB >= 8192 ? 1040 : TB >= 4096 ? 580 : 320;  // >= odd primes in (61, TB]
 constexpr uint32_t kOutWordsPerSeg = (uint32_t)(kWheelOutBits / 32);  // 30720
 

@@ -13,10 +13,13 @@
 //         further mark is one v_add; the 4 lanes of a plane in a half-wave
 //         are 32p periods apart, i.e. in blocks c*p mod 4: distinct banks;
 //      B1 (TA < p <= TB1): one prime per half-wave; lane (plane i, j = 0..3)
-//         takes the hits n with n mod 128 in [32j, 32j+32), in order (3 VALU
-//         per mark), again 32p periods apart: conflict-free;
-//      B2 (TB1 < p <= TB): 8 primes x 8 planes per wave, lane (prime, plane)
-//         walks its plane's hits in order;
+//         takes the hits n with n mod 128 in [32j, 32j+32), by class n mod
+//         128 to the segment end (one v_add per further mark, the marks past
+//         the segment dropped), again 32p periods apart: conflict-free;
+//      B2 (TB1 < p <= TB): one prime per quarter-wave; lane (plane i, j =
+//         0..1) takes the hits n with n mod 64 in [32j, 32j+32), by class to
+//         the segment end as B1; a 32-lane group holds two primes, so a bank
+//         has at most two lanes;
 //      L  (p > TB): one prime per lane, its 8 planes in a lane-rotated order,
 //         starts from the table's wheel offsets with one reduction;
 //   2. expand: lane reads one block (two ds_read_b128) and turns its 8 plane
@@ -214,32 +217,38 @@ __device__ __forceinline__ void mark_at(uint32_t a, uint32_t bit) {
 
 // The hits k + (r + 32 t) p, r = 0..31, t < K, of a lane that walks one
 // plane from k with step p: class r's hits sit D = 32 S p periods apart (S =
-// 1 for a lane that takes consecutive hits, 4 for B1's lanes, which take 32
-// of every 128), so they share their bit and their byte addresses step by D
-// (a period index is its block's byte address): 3 VALU of setup per class,
-// then one v_add per mark (mark_k_step: 3 VALU per mark).
+// 4 for B1's lanes, which take 32 of every 128 hits, 2 for B2's, 32 of every
+// 64), so they share their bit and their byte addresses step by D (a period
+// index is its block's byte address): 3 VALU of setup per class, then one
+// v_add per mark (mark_k_step: 3 VALU per mark).
+// Four classes per asm block and loop iteration (.rept: the K - 1 further
+// marks of a class, and two pairs of classes): one class per iteration pays
+// three SALU of loop control per class, a third of the instructions of a class
+// of two marks. The scratch pairs alternate between classes, as in
+// mark_k_step4.
+#define DSE_CLASS(A, B)                                  \
+  "v_and_or_b32 " A ", %4, %5, %6\n\t"                   \
+  "v_lshlrev_b32 " B ", %4, %7\n\t"                      \
+  "v_add_u32 %4, %4, %8\n\t"                             \
+  "ds_or_b32 " A ", " B " offset:" DSE_IMG_OFF_S "\n\t"  \
+  ".rept %c10\n\t"                                       \
+  "v_add_u32 " A ", " A ", %9\n\t"                       \
+  "ds_or_b32 " A ", " B " offset:" DSE_IMG_OFF_S "\n\t"  \
+  ".endr\n\t"
 template <int K>
 __device__ __forceinline__ void class_marks(uint32_t pb4, uint32_t k, uint32_t p, uint32_t D, uint32_t one) {
 #pragma unroll 1
-  for (uint32_t r = 0; r < 32; ++r) {
-    uint32_t a, b;
-    asm volatile(
-        "v_and_or_b32 %0, %2, %3, %4\n\t"
-        "v_lshlrev_b32 %1, %2, %5\n\t"
-        "ds_or_b32 %0, %1 offset:" DSE_IMG_OFF_S
-        : "=&v"(a), "=&v"(b)
-        : "v"(k), "s"(kBlockMask), "v"(pb4), "v"(one)
-        : "memory");
-#pragma unroll
-    for (int t = 1; t < K; ++t) {
-      a += D;
-      mark_at(a, b);
-    }
-    k = opaque(k + p);
+  for (uint32_t r = 0; r < 32; r += 4) {
+    uint32_t a0, b0, a1, b1;
+    asm volatile(".rept 2\n\t" DSE_CLASS("%0", "%1") DSE_CLASS("%2", "%3") ".endr"
+                 : "=&v"(a0), "=&v"(b0), "=&v"(a1), "=&v"(b1), "+v"(k)
+                 : "s"(kBlockMask), "v"(pb4), "v"(one), "v"(p), "v"(D), "n"(K - 1)
+                 : "memory");
   }
 }
-// K wave-uniform in 1..10 (B1: floor(KP / 128 pmax), B2: floor(KP / 32
-// pmax); 0: nothing)
+// K wave-uniform in 1..kClassMarksMax (B1: floor(floor((KP - 1) / pmin) /
+// 128) + 1, B2: the same with 64; the last mark of a class is dropped where
+// its hit lies past the segment)
 __device__ __forceinline__ void class_marks_k(uint32_t K, uint32_t pb4, uint32_t k, uint32_t p, uint32_t D,
                                               uint32_t one) {
   switch (K) {
@@ -254,6 +263,7 @@ __device__ __forceinline__ void class_marks_k(uint32_t K, uint32_t pb4, uint32_t
     case 8: class_marks<8>(pb4, k, p, D, one); return;
     case 9: class_marks<9>(pb4, k, p, D, one); return;
     case 10: class_marks<10>(pb4, k, p, D, one); return;
+    case 11: class_marks<11>(pb4, k, p, D, one); return;
     default: __builtin_unreachable();
   }
 }
@@ -434,11 +444,11 @@ __device__ __forceinline__ void unit_A(uint32_t img0, uint32_t pi, uint64_t m, c
 }
 
 // B1: two mid primes (TA < p <= TB1), one per half-wave; lane (plane L & 7,
-// j = (L >> 3) & 3) owns the hits n with n mod 128 in [32j, 32j + 32), in
-// order: 32 marks k, k + p, ... then a jump of 96p. The four lanes of a plane
-// are 32p periods apart: distinct banks, as in A. The blocks of 128 hits
-// every lane fills are marked class by class (class_marks); the rest in
-// order with wave-uniform counts, the marks past the segment dropped.
+// j = (L >> 3) & 3) owns the hits n with n mod 128 = 32j + r, r = 0..31. The
+// four lanes of a plane are 32p periods apart: distinct banks, as in A. Every
+// class r is marked to the segment end (class_marks), one mark more than the
+// hits every lane has, dropped where it lies past the segment, as in A: no
+// in-order walk of a last, partly filled block of 128 hits.
 __device__ __forceinline__ void unit_B1(uint32_t img0, const uint32_t* __restrict__ s_mid_p,
                                         const uint64_t* __restrict__ s_mid_m, const MidRes& mr, uint32_t j0,
                                         uint32_t nj, uint64_t Vs, uint64_t rho_pack, uint32_t lane, uint32_t one) {
@@ -460,67 +470,55 @@ __device__ __forceinline__ void unit_B1(uint32_t img0, const uint32_t* __restric
         if (k >= kmin) mark_k(pb4, k, one);
     return;
   }
-  // blocks every lane of the wave fills: n < 128 (t + 1) <= floor(KP / pmax)
-  const uint32_t pmax = __builtin_amdgcn_readlane(p, nj == 2 ? 32 : 0);  // the list ascends
-  // class by class (hits 32j + r + 128t, t < tf: 128p periods apart, one
-  // bit): 1 VALU per mark where walking them takes 3 (1e11: -0.9%)
-  const uint32_t tf = (KP / pmax) / 128;  // wave-uniform (a scalar division)
-  class_marks_k(tf, pb4, k, p, 128 * p, one);
-  k += tf * (128 * p);
-  // the rest: every hit index n of either prime is below n_all = ceil(KP /
-  // pmin) (kp < p), so in each further block of 128 hits lane j marks hits
-  // base + 32j + r, r < min(32, n_all - base), in order; the ones past the
-  // segment are dropped (kImgOff). Wave-uniform counts, no per-lane loop.
+  // class by class (hits 32j + r + 128t: 128p periods apart, one bit): 1
+  // VALU per mark where walking them takes 3. A hit of either prime has k =
+  // kp + n p <= KP - 1, so n <= floor((KP - 1) / pmin) < 128 T: T marks per
+  // class reach every hit, and the marks whose hit does not exist have k >=
+  // KP (below 128 T pmax < 2 KP + 128 pmax) and are dropped (kImgOff). The
+  // unit's first live lane holds pmin (the list ascends).
   const uint32_t pmin = __builtin_amdgcn_readfirstlane(p);
-  const uint32_t n_all = __builtin_amdgcn_readfirstlane(div_ceil_small(KP, pmin, fast_rcp((float)pmin)));
-  for (uint32_t base = 128 * tf; base < n_all; base += 128) {
-    mark_run(pb4, k, p, min(32u, n_all - base), one);
-    k += 128 * p;
-  }
+  const uint32_t T = __builtin_amdgcn_readfirstlane(div_small(KP - 1, pmin, fast_rcp((float)pmin))) / 128 + 1;
+  class_marks_k(T, pb4, k, p, 128 * p, one);
 }
 
-// B2: 8 mid primes (TB1 < p <= TB) x 8 planes; lane (prime L >> 3, plane
-// L & 7) marks its plane's hits: n_u unconditional marks for every lane (the
-// first 32 floor(n_u / 32) class by class), then the rest and the tail up to
-// ceil(KP / pmin) hits as one run (the marks past the segment dropped). A
-// plane's lanes hold different primes, so their banks collide at random (the
-// L pattern).
+// B2: four mid primes (TB1 < p <= TB), one per quarter-wave; lane (prime
+// L >> 4, plane L & 7, j = (L >> 3) & 1) owns the hits n with n mod 64 = 32j
+// + r, r = 0..31, and marks every class r to the segment end as B1 does: T2 =
+// floor(floor((KP - 1) / pmin) / 64) + 1 marks 64p periods apart, the ones
+// past the segment dropped. The two lanes of a prime and plane are 32p
+// periods apart, p blocks: different blocks mod 4 for odd p. A 32-lane group
+// holds two primes, so a bank has at most two lanes (dse_wheel_geometry.h):
+// 1.6 conflict cycles per ds_or where four unrelated primes per plane and
+// half-wave had 3.2.
 __device__ __forceinline__ void unit_B2(uint32_t img0, const uint32_t* __restrict__ s_mid_p,
                                         const uint64_t* __restrict__ s_mid_m, const MidRes& mr, uint32_t j0,
-                                        uint32_t nj, uint64_t Vs, uint64_t Vend, uint64_t rho_pack, uint32_t lane,
-                                        uint32_t one) {
-  const uint32_t pl = lane & 7, jp = lane >> 3;
-  const bool valid = jp < nj;
-  const uint32_t pi = s_mid_p[valid ? j0 + jp : j0];
+                                        uint32_t nj, uint64_t Vs, uint64_t rho_pack, uint32_t lane, uint32_t one) {
+  const uint32_t h = lane >> 4, pl = lane & 7, j = (lane >> 3) & 1;
+  if (h >= nj) return;  // the quarter-waves past the list end mark nothing
+  const uint32_t pi = s_mid_p[j0 + h];
   const uint32_t p = pi & 0xFFFFu, inv30 = pi >> 16;
-  const uint64_t m = s_mid_m[valid ? j0 + jp : j0];
+  const uint64_t m = s_mid_m[j0 + h];
   const float invp = fast_rcp((float)p);
   const uint32_t rho = (uint32_t)(rho_pack >> (5 * pl)) & 31u;
-  uint32_t k = plane_first(mid_residue(mr, valid ? j0 + jp : j0, p, m, Vs, valid && pl == 0), rho, p, inv30, invp);
-  const uint64_t p2 = (uint64_t)p * p;
-  const bool slow = p2 > Vs;
-  if (slow) k = p2 >= Vend ? KP : first_at_or_after(k, kmin_for((uint32_t)(p2 - Vs), rho), p, invp);
-  const uint32_t pmax = __builtin_amdgcn_readfirstlane(s_mid_p[j0 + nj - 1]) & 0xFFFFu;
-  const bool any_slow = __builtin_amdgcn_ballot_w64(slow) != 0;
-  const uint32_t n_u = any_slow ? 0u : KP / pmax;  // every lane has >= floor(KP / p) of them (k < p)
+  const uint32_t kp = plane_first(mid_residue(mr, j0 + h, p, m, Vs, (lane & 15) == 0), rho, p, inv30, invp);
   const uint32_t pb4 = img0 + 4 * pl;
-  // lanes past the batch end mark nothing (their unconditional marks would
-  // land in another prime's plane)
-  if (!valid) return;
-  // the first 32 K of the n_u unconditional hits class by class (hits r +
-  // 32t, t < K: 32p periods apart, one bit), the rest in order
-  const uint32_t K = n_u / 32;
-  class_marks_k(K, pb4, k, p, 32 * p, one);
-  k += K * (32 * p);
-  if (any_slow) {
-    mark_tail(pb4, mark_run(pb4, k, p, n_u - 32 * K, one), p, one);
+  uint32_t k = kp + 32 * j * p;                          // hit n = 32j
+  // the list ascends: pmax decides for the wave whether some p^2 lies inside
+  // the segment
+  const uint32_t pmax = __builtin_amdgcn_readfirstlane(s_mid_p[j0 + nj - 1]) & 0xFFFFu;
+  if ((uint64_t)pmax * pmax > Vs) {  // one at a time from kmin (0 for the primes with p^2 <= Vs)
+    const uint64_t p2 = (uint64_t)p * p;
+    const uint32_t kmin = p2 > Vs ? kmin_for((uint32_t)min(p2 - Vs, (uint64_t)0xFFFFFFFFu), rho) : 0u;
+    for (; k < KP; k += 32 * p)
+      for (uint32_t r = 0; r < 32 && k < KP; ++r, k += p)
+        if (k >= kmin) mark_k(pb4, k, one);
     return;
   }
-  // every lane has fewer than n_all = ceil(KP / pmin) hits (k < p): the rest
-  // as one run, the marks past the segment dropped (kImgOff)
-  const uint32_t pmin = __builtin_amdgcn_readfirstlane(s_mid_p[j0]) & 0xFFFFu;
-  const uint32_t n_all = __builtin_amdgcn_readfirstlane(div_ceil_small(KP, pmin, fast_rcp((float)pmin)));
-  mark_run(pb4, k, p, n_all - 32 * K, one);
+  // a hit has k = kp + n p <= KP - 1, so n <= floor((KP - 1) / pmin) < 64 T2;
+  // lane 0 holds pmin
+  const uint32_t pmin = __builtin_amdgcn_readfirstlane(p);
+  const uint32_t T2 = __builtin_amdgcn_readfirstlane(div_small(KP - 1, pmin, fast_rcp((float)pmin))) / 64 + 1;
+  class_marks_k(T2, pb4, k, p, 64 * p, one);
 }
 
 // Operands of one large unit, loaded ahead of use. The table row of prime i
@@ -889,7 +887,7 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     lds.mid_inc[i] = (uint32_t)(((uint64_t)gridDim.x * kWheelSpan) % q);
   }
   // Work units: list 1 = nA single mid primes (A), nB1 units of two primes
-  // (B1), nB2 units of 8 primes (B2); list 2 = nL large units (two sets of 64
+  // (B1), nB2 units of 4 primes (B2); list 2 = nL large units (two sets of 64
   // primes each); handed out through one dynamic queue. Issue arbitration
   // favours older waves, so any static split finishes the youngest waves
   // last; the queue makes them take fewer units instead.
@@ -897,7 +895,7 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
   const uint32_t n_mid = i_mid1 - i_mid0;
   const uint32_t n_b1 = i_midB2 - i_mid0;      // staged index where B2 starts
   const uint32_t nB1 = (i_midB2 - i_midB + 1) / 2;
-  const uint32_t nB2 = (i_mid1 - i_midB2 + 7) / 8;
+  const uint32_t nB2 = (i_mid1 - i_midB2 + 3) / 4;
   const uint32_t i_big = s_thr[4];             // L units end here
   constexpr uint32_t kLU = 128;                // primes per L unit
   const uint32_t n1 = nA + nB1 + nB2;
@@ -1290,10 +1288,10 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
           if ((uint64_t)pf * pf < Vend)
             unit_B1(img0, s_mid_p, s_mid_m, mr, j0, min(2u, n_b1 - j0), Vs, rg.rho_pack, lane, one);
         } else {
-          const uint32_t j0 = n_b1 + (k - nA - nB1) * 8;
+          const uint32_t j0 = n_b1 + (k - nA - nB1) * 4;
           const uint32_t pf = __builtin_amdgcn_readfirstlane(s_mid_p[j0]) & 0xFFFFu;
           if ((uint64_t)pf * pf < Vend)
-            unit_B2(img0, s_mid_p, s_mid_m, mr, j0, min(8u, n_mid - j0), Vs, Vend, rg.rho_pack, lane, one);
+            unit_B2(img0, s_mid_p, s_mid_m, mr, j0, min(4u, n_mid - j0), Vs, rg.rho_pack, lane, one);
         }
       } else {
         // a set marks if its first prime's square is below the segment's end
