@@ -704,6 +704,8 @@ hipError_t ensure_scratch(Scratch* sc, uint64_t bytes, hipStream_t stream, char*
 }  // namespace
 
 // A range whose primes reach above kWheelMaxPrime: bucketed passes.
+// tests/max_pass_ref.py (planned_passes) restates the pass planning, bucket_cap, bucket_k0 and the
+// scratch layout below for the tests of the largest passes: change them together.
 hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, uint32_t* out,
                            unsigned long long* count, int num_cus, hipStream_t stream, Scratch* scratch,
                            const SieveOpts* opts, PlanStats* plan) {
@@ -805,6 +807,9 @@ hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, 
       return fail_pass(e);
     hipLaunchKernelGGL(bucket_fill_stage_kernel, dim3(nfill + (band1 ? kBucketGrid1 : 0)), dim3(kBucketThreads),
                        lds_bytes, stream, table, ba, range, cols, start, bz, tmp, nsup, nfill, scratch->flag);
+    // defensive (no refusal has been seen: the runtime launches 66,816 bytes of LDS even
+    // without the opt-in): had this launch failed, the sort would run over unwritten keys
+    if ((e = hipGetLastError()) != hipSuccess) return fail_pass(e);
     if (band1) {
       hipLaunchKernelGGL(bucket_sort_kernel, dim3(nsup * (kBucketGrid1 / kSortGroup)), dim3(kSortThreads), 0,
                          stream, ba, cols, start, tmp, ent, scratch->flag);
@@ -825,6 +830,7 @@ hipError_t launch_bucketed(const void* table, uint64_t g_start, uint64_t nbits, 
       plan->add_wheel_launch(wa.nseg, wheel_grid(wa.nseg, num_cus));
       ++plan->bucket_passes;
       plan->bucket_max_pass_segments = std::max(plan->bucket_max_pass_segments, ns);
+      plan->bucket_max_lds_bytes = std::max<uint64_t>(plan->bucket_max_lds_bytes, lds_bytes);
     }
     s0 += ns;
   }

@@ -919,6 +919,8 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
     *value = (int64_t)ctx->plan.bucket_passes;
   } else if (n == "plan_bucket_max_pass_segments") {
     *value = (int64_t)ctx->plan.bucket_max_pass_segments;
+  } else if (n == "plan_bucket_max_lds_bytes") {
+    *value = (int64_t)ctx->plan.bucket_max_lds_bytes;
   } else if (n == "primes_tile_bits") {
     *value = (int64_t)kMaskTileBits;
   } else if (n == "stats_tile_bits") {

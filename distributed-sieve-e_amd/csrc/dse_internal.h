@@ -147,6 +147,7 @@ struct PlanStats {
   uint64_t max_rounds = 0;              // largest ceil(segments / workgroups) of a wheel launch
   uint64_t bucket_passes = 0;           // bucketed passes
   uint64_t bucket_max_pass_segments = 0;  // segments of the largest one
+  uint64_t bucket_max_lds_bytes = 0;      // largest dynamic LDS size given to bucket_fill_stage_kernel
   // one wheel launch of `nseg` segments over `grid` workgroups (wheel_grid)
   void add_wheel_launch(uint32_t nseg, uint32_t grid) {
     ++wheel_launches;

@@ -97,29 +97,42 @@ def wheel_marks_for_range(g_start: int, nbits: int) -> int:
 
 
 BUCKET_LO = 2**19  # ranges with bucketed primes bucket every prime above this (csrc kBucketLoLog)
+BUCKET_SPLIT = 2**28  # bucketed primes up to this are band 0 (one-level fill), above it band 1 (csrc kBucketSplitLog)
 
 
-def bucket_entries_for_range(g_start: int, nbits: int, lo_p: int = BUCKET_LO) -> int:
-    """Bucket entries the bucketed pass writes (and the wheel kernel reads
-    back) for the odd-index range: one per multiple p*m in the range with
-    gcd(m, 30) = 1 and p*m >= p^2 of every prime lo_p < p <= sqrt(vmax)
+def bucket_band_entries_for_range(g_start: int, nbits: int, lo_p: int = BUCKET_LO, split: int = BUCKET_SPLIT):
+    """(band 0, band 1) bucket entries the bucketed passes write (and the wheel
+    kernel reads back) for the odd-index range: one per multiple p*m in the
+    range with gcd(m, 30) = 1 and p*m >= p^2 of every prime lo_p < p <=
+    sqrt(vmax), band 0 the primes up to `split`, band 1 those above it
     (csrc/dse_bucket.hip bucket_fill_stage_kernel; the range must reach past
-    2^20, or the wheel kernel takes all its primes itself). Needs the primes up
-    to sqrt(vmax): ~0.5 GB and ~10 s of numpy for the 1e18 window
-    (tools/window_entries.py keeps that one as WINDOW_BUCKET_ENTRIES)."""
+    2^20, or the wheel kernel takes all its primes itself). The totals do not
+    depend on how the range is cut into passes. Needs the primes up to
+    sqrt(vmax): ~0.5 GB and ~10 s of numpy for the 1e18 window
+    (tools/window_entries.py keeps that one as WINDOW_BUCKET_ENTRIES), ~2 GB
+    and a minute at the top of the range (primes to 2^31)."""
     if nbits <= 0:
-        return 0
+        return 0, 0
     va = 3 + 2 * g_start
     vb = 3 + 2 * (g_start + nbits - 1)
     ps = odd_primes_upto(math.isqrt(vb))
     ps = ps[ps > lo_p]
-    if ps.size == 0:
-        return 0
-    lo = np.maximum(ps * ps, va)
-    m0 = (lo + ps - 1) // ps
-    m1 = vb // ps
-    cnt = np.where(m1 >= m0, _coprime30_upto(m1) - _coprime30_upto(m0 - 1), 0)
-    return int(cnt.sum())
+    bands = [0, 0]
+    for i in range(0, ps.size, 1 << 24):  # in pieces: the temporaries of 1e8 primes would take gigabytes
+        q = ps[i:i + (1 << 24)]
+        lo = np.maximum(q * q, va)
+        m0 = (lo + q - 1) // q
+        m1 = vb // q
+        cnt = np.where(m1 >= m0, _coprime30_upto(m1) - _coprime30_upto(m0 - 1), 0)
+        one = q > split
+        bands[1] += int(cnt[one].sum())
+        bands[0] += int(cnt[~one].sum())
+    return bands[0], bands[1]
+
+
+def bucket_entries_for_range(g_start: int, nbits: int, lo_p: int = BUCKET_LO) -> int:
+    """All bucket entries of the range, both bands (bucket_band_entries_for_range)."""
+    return sum(bucket_band_entries_for_range(g_start, nbits, lo_p))
 
 
 # bucket_entries_for_range of bench.py --window's range (odd values 1e18 + 1 ..

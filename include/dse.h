@@ -784,7 +784,11 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   launch, workgroups = min(segments, CUs): above 1, workgroups carried
  *   state from one segment to their next;
  *   "plan_bucket_passes": bucketed passes;
- *   "plan_bucket_max_pass_segments": the largest of them, in segments.
+ *   "plan_bucket_max_pass_segments": the largest of them, in segments;
+ *   "plan_bucket_max_lds_bytes": the largest dynamic LDS size a pass gave to
+ *   its fill-and-stage launch, in bytes (above 65,536 the launch needs the
+ *   kernel's opt-in to more dynamic LDS: passes of more than 7,936 segments
+ *   with band-1 primes).
  * DSE_EINVAL for an unknown name. */
 int32_t dse_debug_get_stat(dse_ctx *ctx, const char *name, int64_t *value);
 

@@ -29,6 +29,9 @@
  *           cross-checked against ref_* in tests/test_oracle.py.
  *   fast_count_window  an independent OpenMP count of the primes in a high
  *           window (outside the reference's semantics).
+ *   fast_mask_window  the same sieve (one body, window_sieve) returning its
+ *           mask in fast_sieve_range's layout: the reference for passes of
+ *           thousands of wheel segments (tests/golden/max_pass.json).
  */
 #include <math.h>
 #include <pthread.h>
@@ -238,6 +241,34 @@ static uint32_t *fast_base_primes(uint64_t limit, uint64_t *np_out) {
   return pr;
 }
 
+/* The base primes of the largest limit asked for so far, kept for the life of
+ * the library: those of a smaller limit are a prefix of them, and a test that
+ * runs three sieves at 1e18 pays for one table (9 s to 1e9, 20 s to 2^31 on
+ * one thread), not three. base_primes_acquire returns with base_mu held, so a
+ * caller that grows the table cannot free it under another; every exit of the
+ * caller goes through base_primes_release. */
+static pthread_mutex_t base_mu = PTHREAD_MUTEX_INITIALIZER;
+static uint32_t *base_pr;
+static uint64_t base_np, base_limit;
+
+static const uint32_t *base_primes_acquire(uint64_t limit, uint64_t *np_out) {
+  pthread_mutex_lock(&base_mu);
+  if (!base_pr || limit > base_limit) {
+    free(base_pr);
+    base_pr = fast_base_primes(limit, &base_np);
+    base_limit = limit;
+  }
+  uint64_t lo = 0, hi = base_pr ? base_np : 0; /* first index with p > limit */
+  while (lo < hi) {
+    uint64_t mid = (lo + hi) / 2;
+    if (base_pr[mid] <= limit) lo = mid + 1; else hi = mid;
+  }
+  *np_out = lo;
+  return base_pr;
+}
+
+static void base_primes_release(void) { pthread_mutex_unlock(&base_mu); }
+
 static uint64_t isqrt_u64(uint64_t x) {
   uint64_t r = (uint64_t)sqrtl((long double)x);
   while (r * r > x) --r;
@@ -249,7 +280,8 @@ int fast_sieve_range(uint64_t g0, uint64_t nbits, uint64_t *mask, uint64_t *coun
   if (nbits == 0) { if (count) *count = 0; return REF_OK; }
   uint64_t vmax = 3 + 2 * (g0 + nbits - 1);
   uint64_t np;
-  uint32_t *pr = fast_base_primes(isqrt_u64(vmax), &np);
+  const uint32_t *pr = base_primes_acquire(isqrt_u64(vmax), &np);
+  if (!pr) { base_primes_release(); return REF_ENOMEM; }
   const uint64_t SEG = 1ull << 18; /* bits per segment, multiple of 64 */
   uint64_t nseg = (nbits + SEG - 1) / SEG;
   uint64_t total = 0;
@@ -278,7 +310,7 @@ int fast_sieve_range(uint64_t g0, uint64_t nbits, uint64_t *mask, uint64_t *coun
     }
     free(s);
   }
-  free(pr);
+  base_primes_release();
   if (count) *count = total;
   return REF_OK;
 }
@@ -549,24 +581,29 @@ static uint64_t first_off(uint64_t a, uint64_t p) {
   return (w - a) / 2;
 }
 
-int fast_count_window(uint64_t lo, uint64_t hi, uint64_t *count) {
-  if (!count) return REF_EINVAL;
-  *count = 0;
-  uint64_t a = lo < 3 ? 3 : lo;
-  if (!(a & 1)) ++a;
-  if (hi < a) return REF_OK;
-  uint64_t b = (hi & 1) ? hi : hi - 1;
-  uint64_t nb = (b - a) / 2 + 1; /* odd values a, a+2, ..., b */
+/* The window sieve's one body: odd values a, a + 2, ..., nb of them (a odd,
+ * a >= 3). mask (nullable): ceil(nb / 64) words, bit j <-> value a + 2j,
+ * 1 = prime, bits past nb zero -- fast_sieve_range's layout. Thread slices
+ * are multiples of 64 bits, so no two threads share a word of the mask: a
+ * thread marks composites straight into its slice of it and inverts the slice
+ * at the end (no mask: a slice of its own). nthreads <= 0: OpenMP's default. */
+static int window_sieve(uint64_t a, uint64_t nb, uint64_t *mask, uint64_t *count, int nthreads) {
+  const uint64_t b = a + 2 * (nb - 1);
   uint64_t np;
-  uint32_t *pr = fast_base_primes(isqrt_u64(b), &np);
-  if (!pr) return REF_ENOMEM;
+  const uint32_t *pr = base_primes_acquire(isqrt_u64(b), &np);
+  if (!pr) { base_primes_release(); return REF_ENOMEM; }
   const uint64_t SMALL = 1ull << 22, SEG = 1ull << 21; /* bits */
   uint64_t nsmall = 0;
   while (nsmall < np && pr[nsmall] < SMALL) ++nsmall;
   uint64_t total = 0;
   int err = 0;
   (void)mulmod_u64;
-#pragma omp parallel reduction(+ : total)
+#ifdef _OPENMP
+  if (nthreads <= 0) nthreads = omp_get_max_threads();
+#else
+  nthreads = 1;
+#endif
+#pragma omp parallel reduction(+ : total) num_threads(nthreads)
   {
     int nt = 1, t = 0;
 #ifdef _OPENMP
@@ -578,12 +615,13 @@ int fast_count_window(uint64_t lo, uint64_t hi, uint64_t *count) {
     uint64_t s0 = per * (uint64_t)t, s1 = s0 + per < nb ? s0 + per : nb;
     if (s0 < s1) {
       uint64_t len = s1 - s0, words = (len + 63) / 64;
-      uint64_t *bits = (uint64_t *)calloc(words, 8); /* 1 = composite */
+      uint64_t *bits = mask ? mask + s0 / 64 : (uint64_t *)calloc(words, 8); /* 1 = composite */
       uint64_t *off = (uint64_t *)malloc((nsmall ? nsmall : 1) * 8);
       if (!bits || !off) {
 #pragma omp atomic write
         err = REF_ENOMEM;
       } else {
+        if (mask) memset(bits, 0, words * 8);
         const uint64_t va = a + 2 * s0; /* value of bit 0 */
         for (uint64_t i = 0; i < nsmall; ++i) off[i] = first_off(va, pr[i]);
         for (uint64_t g = 0; g < len; g += SEG) { /* small primes, segment by segment */
@@ -603,6 +641,7 @@ int fast_count_window(uint64_t lo, uint64_t hi, uint64_t *count) {
         for (uint64_t w = 0; w < words; ++w) {
           uint64_t v = ~bits[w];
           if (w == words - 1 && (len & 63)) v &= (1ull << (len & 63)) - 1;
+          if (mask) bits[w] = v;
           c += (uint64_t)__builtin_popcountll(v);
         }
         /* values that are small primes themselves (windows starting below
@@ -610,12 +649,42 @@ int fast_count_window(uint64_t lo, uint64_t hi, uint64_t *count) {
          * prime but a >= 3 excludes it */
         total += c;
       }
-      free(bits);
+      if (!mask) free(bits);
       free(off);
     }
   }
-  free(pr);
+  base_primes_release();
   if (err) return err;
-  *count = total;
+  if (count) *count = total;
   return REF_OK;
+}
+
+int fast_count_window(uint64_t lo, uint64_t hi, uint64_t *count) {
+  if (!count) return REF_EINVAL;
+  *count = 0;
+  uint64_t a = lo < 3 ? 3 : lo;
+  if (!(a & 1)) ++a;
+  if (hi < a) return REF_OK;
+  uint64_t b = (hi & 1) ? hi : hi - 1;
+  return window_sieve(a, (b - a) / 2 + 1, NULL, count, 0);
+}
+
+/* ---------------------------------------------------------------------
+ * fast_mask_window: fast_count_window's sieve in fast_sieve_range's
+ * coordinates and layout: odd indices [g0, g0 + nbits), bit j <-> value
+ * 3 + 2 (g0 + j), 1 = prime, ceil(nbits / 64) packed uint64 words. mask may be
+ * NULL (count only). It marks the large primes directly, so a pass of 8,192
+ * wheel segments at 1e18 takes a minute where fast_sieve_range, which visits
+ * every prime in every 2^18-bit segment, takes hours. The _nt form fixes the
+ * number of threads (the slice boundaries depend on it; the result must not).
+ * --------------------------------------------------------------------- */
+int fast_mask_window_nt(uint64_t g0, uint64_t nbits, uint64_t *mask, uint64_t *count, int32_t nthreads) {
+  if (count) *count = 0;
+  if (nbits == 0) return REF_OK;
+  if (g0 > (1ull << 62) || nbits > (1ull << 62) - g0) return REF_EINVAL; /* 3 + 2 g in 64 bits */
+  return window_sieve(3 + 2 * g0, nbits, mask, count, nthreads);
+}
+
+int fast_mask_window(uint64_t g0, uint64_t nbits, uint64_t *mask, uint64_t *count) {
+  return fast_mask_window_nt(g0, nbits, mask, count, 0);
 }

@@ -41,8 +41,10 @@ def lib() -> ctypes.CDLL:
         L.fast_sieve_range.argtypes = [u64, u64, pu64, pu64]
         L.ref_sieve_threaded.argtypes = [i64, i32, pu64, pu64, p64, pu64]
         L.fast_count_window.argtypes = [u64, u64, pu64]
+        L.fast_mask_window.argtypes = [u64, u64, pu64, pu64]
+        L.fast_mask_window_nt.argtypes = [u64, u64, pu64, pu64, i32]
         for f in (L.ref_spread_work, L.ref_sieve, L.ref_sieve_flags, L.ref_finish, L.fast_sieve_range,
-                  L.ref_sieve_threaded, L.fast_count_window):
+                  L.ref_sieve_threaded, L.fast_count_window, L.fast_mask_window, L.fast_mask_window_nt):
             f.restype = ctypes.c_int
         _lib = L
     return _lib
@@ -112,6 +114,28 @@ def count_window(lo: int, hi: int) -> int:
     if rc:
         raise RuntimeError(f"fast_count_window rc={rc}")
     return cnt.value
+
+
+def mask_window(g0: int, nbits: int, want_mask: bool = True, threads: int = 0):
+    """count_window's sieve (one body in dse_oracle.c) over the odd indices
+    [g0, g0 + nbits): bit j <-> value 3 + 2 (g0 + j), 1 = prime, in
+    fast_sieve_range's packed layout. It marks large primes directly, so it
+    reaches ranges of 1e10 candidates at 1e18 in a minute. threads > 0 fixes
+    the number of OpenMP threads (the result does not depend on it).
+
+    Like fast_sieve_range and count_window it takes its base primes from a
+    table the library keeps for the rest of the process (the largest limit
+    asked for so far: 200 MB after a sieve at 1e18, 420 MB at the top of the
+    range) and holds the library's lock while it runs, so oracle calls from
+    several Python threads run one after another.
+
+    Returns (mask or None, count)."""
+    mask = np.empty(words_for(nbits), dtype=np.uint64) if want_mask else None
+    cnt = ctypes.c_uint64()
+    rc = lib().fast_mask_window_nt(g0, nbits, _p(mask, ctypes.c_uint64), ctypes.byref(cnt), threads)
+    if rc:
+        raise RuntimeError(f"fast_mask_window rc={rc}")
+    return mask, cnt.value
 
 
 def pi_ref(counts) -> int:

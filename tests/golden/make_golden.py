@@ -231,6 +231,99 @@ def rounds(g: dict) -> None:
     g["rounds"] = res
 
 
+MAXPASS_OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "max_pass.json")
+MAXPASS_PIECE_SEGS = 128                     # segments per hashed piece: one super-bucket of a pass from g0
+_G0_1E18 = (10**18 + 1 - 3) // 2
+MAXPASS = {                                  # name: (g0, nb, bucket_lo_log2, bucket_split_log2 of the entry counts)
+    "window_1e18": (_G0_1E18, (10**18 + 10**10 - 1 - (10**18 + 1)) // 2 + 1, 19, 28),   # bench.py --window's range
+    "max_1e18": (_G0_1E18 + 12345, 8192 * TOP_SEG_BITS + 130 * TOP_SEG_BITS + 777, 19, 28),
+    # ends at 2^62 - 1. Its first 8,192 segments have 8.7e8 band-1 entries (the 1.9e9 of a pass's capacity
+    # there is a bound, not a count), so the range runs on for 2,049 segments more: above 2^30 in all
+    "max_top": (2**61 - 1 - ((8192 + 2048) * TOP_SEG_BITS + 777), (8192 + 2048) * TOP_SEG_BITS + 777, 19, 28),
+    # where a pass of 8,192 segments can run at all: with every bucketed prime in band 1 (both test options
+    # 2^20) the planner keeps it up to values of 1.7e15; at 1e15 it holds 1.9e9 band-1 entries
+    "max_1e15": (10**15 // 2 + 12345, 8192 * TOP_SEG_BITS + 130 * TOP_SEG_BITS + 777, 20, 20),
+}
+MAXPASS_SEGS = 8192                          # the planner's largest pass (csrc kBucketMaxSegs)
+
+
+def maxpass_entry(name: str, g0: int, nb: int, lo_log2: int, split_log2: int) -> dict:
+    """One entry of max_pass.json from oracle.mask_window: the count, the primes
+    of every segment of 1,966,080 candidates from g0 on, one SHA-256 per 128
+    segments of mask (the last piece shorter) and the exact bucket entries of
+    the two bands (mail_sieve_e.work). 4,096 seeded random candidates are
+    checked against deterministic Miller-Rabin before anything is returned.
+    The entries are those of the bucketed primes above 2^lo_log2, split into
+    the bands at 2^split_log2 (19 and 28: production); first_pass_*: those of
+    the first 8,192 segments."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "distributed-sieve-e_amd"))
+    from mail_sieve_e import work
+    from primes_ref import is_prime_mr
+    t = time.time()
+    m, c = o.mask_window(g0, nb)
+    t_mask = time.time() - t
+    for j in np.random.default_rng(0x5EED).integers(0, nb, 4096):
+        j = int(j)
+        assert bool(int(m[j >> 6]) >> (j & 63) & 1) == is_prime_mr(3 + 2 * (g0 + j)), (name, 3 + 2 * (g0 + j))
+    seg_words = TOP_SEG_BITS // 64
+    piece_words = MAXPASS_PIECE_SEGS * seg_words
+    seg, hashes = [], []
+    for w0 in range(0, len(m), piece_words):
+        piece = m[w0:w0 + piece_words]
+        hashes.append(sha(piece))
+        pc = np.bitwise_count(piece).astype(np.int64)
+        pc = np.concatenate([pc, np.zeros(-len(pc) % seg_words, dtype=np.int64)])  # the ragged last segment
+        seg += [int(x) for x in pc.reshape(-1, seg_words).sum(axis=1)]
+    assert len(seg) == -(-nb // TOP_SEG_BITS) and sum(seg) == int(c)
+    t = time.time()
+    lo_p, split = 2**lo_log2, 2**split_log2
+    band0, band1 = work.bucket_band_entries_for_range(g0, nb, lo_p, split)
+    first = work.bucket_band_entries_for_range(g0, min(nb, MAXPASS_SEGS * TOP_SEG_BITS), lo_p, split) \
+        if len(seg) > MAXPASS_SEGS else (band0, band1)
+    t_entries = time.time() - t
+    print(f"maxpass {name}: {int(c)} primes in {len(seg)} segments, band-0 entries {band0}, band-1 entries {band1} "
+          f"({first[0]} and {first[1]} in the first pass; mask {t_mask:.1f}s, entries {t_entries:.1f}s)", flush=True)
+    return {"g0": g0, "nb": nb, "count": int(c), "segment_counts": seg, "piece_sha256": hashes,
+            "bucket_lo_log2": lo_log2, "bucket_split_log2": split_log2,
+            "band0_entries": band0, "band1_entries": band1,
+            "first_pass_band0_entries": first[0], "first_pass_band1_entries": first[1],
+            "source": "oracle.mask_window (fast_mask_window, the body of fast_count_window), 4,096 seeded random "
+                      "candidates checked against Miller-Rabin (tests/primes_ref.py) when generated; entries by "
+                      "mail_sieve_e.work.bucket_band_entries_for_range"}
+
+
+def maxpass_json(res: dict) -> str:
+    """max_pass.json's text: one line per field, a list of 10,000 counts on one
+    line too, so the file is a few dozen lines."""
+    def field(k, v, pad):
+        return f'{pad}{json.dumps(k)}: {json.dumps(v, separators=(",", ":"))}'
+    lines = []
+    for k, v in res.items():
+        if isinstance(v, dict):
+            lines.append(f' {json.dumps(k)}: {{\n' + ",\n".join(field(a, b, "  ") for a, b in v.items()) + "\n }")
+        else:
+            lines.append(field(k, v, " "))
+    return "{\n" + ",\n".join(lines) + "\n}\n"
+
+
+def maxpass() -> None:
+    """tests/golden/max_pass.json: the bench window and two ranges of more than
+    8,192 segments (kBucketMaxSegs), at 1e18, ending at 2^62 - 1 and at 1e15."""
+    res = {"generator": "tests/golden/make_golden.py --maxpass", "oracle": "oracle/dse_oracle.c",
+           "seg_bits": TOP_SEG_BITS, "piece_segments": MAXPASS_PIECE_SEGS}
+    for name, (g0, nb, lo_log2, split_log2) in MAXPASS.items():
+        res[name] = maxpass_entry(name, g0, nb, lo_log2, split_log2)
+    assert res["window_1e18"]["count"] == 241_272_176, res["window_1e18"]["count"]
+    assert 3 + 2 * (res["max_top"]["g0"] + res["max_top"]["nb"] - 1) == 2**62 - 1
+    assert res["max_top"]["band1_entries"] > 2**30, res["max_top"]["band1_entries"]
+    # the pass whose 32-bit sums are the largest the planner allows (DESIGN.md section 4.3)
+    assert res["max_1e15"]["first_pass_band1_entries"] > 2**30, res["max_1e15"]["first_pass_band1_entries"]
+    with open(MAXPASS_OUT, "w") as f:
+        f.write(maxpass_json(res))
+    print("wrote", MAXPASS_OUT)
+
+
 def main():
     """Default: regenerate the small fixtures (sweep, files, 1e9). Flags add or
     refresh sections of the existing golden.json in place:
@@ -240,8 +333,16 @@ def main():
       --big12    1e12 P=8 (streamed, ~10 min on 8 cores)
       --window   the [1e18, 1e18+1e10] count
       --top      base-table primes to 1e9 and 2^31 - 1, and the last segments below 2^62
-      --rounds   261 bucketed segments at 1e16 and at 1e18 (about 3 min of oracle time)"""
+      --rounds   261 bucketed segments at 1e16 and at 1e18 (about 3 min of oracle time)
+    --maxpass alone writes tests/golden/max_pass.json and leaves golden.json as it is: the bench
+    window (2,544 segments), 8,192 + 131 segments at 1e18 and at 1e15, and 8,192 + 2,049 ending at
+    2^62 - 1. Measured on 8 cores: masks 15 s, 25 s, 11 s and 38 s (the last with base primes to
+    2^31 - 1), entry counts 13 s, 26 s, 1 s and 55 s of numpy; 3.5 min in all, 5 GB of memory."""
     flags = set(sys.argv[1:])
+    if "--maxpass" in flags:
+        assert flags == {"--maxpass"}, "--maxpass runs alone"
+        maxpass()
+        return
     incremental = flags & {"--ref1e10", "--big11", "--big12", "--window", "--top", "--rounds"}
     if incremental and os.path.exists(OUT):
         g = json.load(open(OUT))

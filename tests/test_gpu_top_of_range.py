@@ -175,6 +175,31 @@ def test_segments_at_the_top(top_ctx, mr_cache, option, value):
     assert sha(m) == g["mask_sha256"]
 
 
+def test_largest_passes_at_the_top(top_ctx, table_m):
+    """8,192 + 2,049 segments ending at 2^62 - 1 (tests/golden/max_pass.json
+    "max_top", the oracle's window sieve with base primes to 2^31 - 1) with the
+    production options on the 2^31 - 1 table. The planner halves what would be
+    passes of 8,192 and 6,145 segments (band-0 regions above 24 GiB) and runs
+    4,096 + 3,072 + 3,073: where primes reach 2^31 a pass has the most entries
+    a production pass has, 4.4e8 in band 1 and 1.7e9 in band 0, in the 32-bit
+    sums of the bucket kernels, in 45 GiB of scratch. Every segment's primes,
+    the count and a SHA-256 per 128 segments of mask (tests/max_pass_ref.py)."""
+    import max_pass_ref as R
+    e = R.FIX["max_top"]
+    g0, nb = e["g0"], e["nb"]
+    assert 3 + 2 * (g0 + nb - 1) == 2**62 - 1 and len(e["segment_counts"]) == R.MAX_PASS + 2049
+    # read from the fixture, so that another range cannot quietly make the case small
+    assert e["band1_entries"] > 2**30 and e["first_pass_band1_entries"] > 2**29
+    R.need_device_memory(g0, nb)
+    passes = R.planned_passes(g0, nb)
+    assert [p[0] for p in passes] == [4096, 3072, 3073] and max(p[2] for p in passes) <= R.MAX_ENTRIES
+    mask, c = R.sieve_dev(top_ctx, table_m["t"].data_ptr(), g0, nb)
+    plan = tuple(top_ctx.debug_get_stat(k) for k in ("plan_bucket_passes", "plan_bucket_max_pass_segments",
+                                                     "plan_bucket_max_lds_bytes"))
+    assert plan == (3, 4096, R.stage_lds_bytes(4096)) and plan[2] == 33_408, plan
+    R.check_entry(mask, c, e, passes=[p[0] for p in passes], what="8,192 + 2,049 segments ending at 2^62 - 1")
+
+
 # ---- the base table, pinned whole ------------------------------------------
 
 def _hash_primes(t, count, step=1 << 24):

@@ -227,3 +227,104 @@ def test_golden_rounds_entries():
         assert all(0 < c < 1_966_080 for c in e["segment_counts"][:-1]) and 0 <= e["segment_counts"][-1] <= 777
         assert abs(e["count"] / (e["nb"] * 2 / math.log(2 * e["g0"])) - 1) < 0.01
         assert len(e["mask_sha256"]) == 64 and "Miller-Rabin" in e["source"]
+
+
+# ---- fast_mask_window: the window sieve returning its mask ----------------------
+
+_OSEG = 1 << 18                                # fast_sieve_range's segment, in bits
+# (g0, nbits): from 0 (the p^2 starts; the small primes stay set), ragged at
+# 1e13 (sieving primes below 2^22 only), at 1e15 (primes up to 3.2e7: the
+# directly marked ones), two oracle segments at 1e18, and ending at index
+# 2^61 - 2 (value 2^62 - 1, base primes to 2^31 - 1)
+_MW = {
+    "from0": (0, 4 * _OSEG + 777),
+    "1e13": ((10**13 + 1 - 3) // 2 + 12345, 3 * _OSEG + 777),
+    "1e15": ((10**15 + 1 - 3) // 2 + 12345, 3 * _OSEG + 777),
+    "1e18": ((10**18 + 1 - 3) // 2, 2 * _OSEG),
+    "top": (2**61 - 1 - (_OSEG + 777), _OSEG + 777),
+}
+
+
+def _mask_window_case(oracle, name):
+    """mask_window against fast_sieve_range word for word, count_window on the
+    same [lo, hi], and 4,096 seeded candidates against Miller-Rabin."""
+    from primes_ref import is_prime_mr, mask_bits
+    g0, nb = _MW[name]
+    m, c = oracle.mask_window(g0, nb)
+    m_ref, c_ref = oracle.fast_sieve_range(g0, nb)
+    assert m.shape == m_ref.shape == ((nb + 63) // 64,)
+    bad = np.flatnonzero(m != m_ref)
+    assert len(bad) == 0, (name, int(bad[0]), hex(int(m[bad[0]])), hex(int(m_ref[bad[0]])))
+    assert c == c_ref
+    assert oracle.mask_window(g0, nb, want_mask=False) == (None, c)
+    lo, hi = 3 + 2 * g0, 3 + 2 * (g0 + nb - 1)
+    assert oracle.count_window(lo, hi) == oracle.count_window(lo - 1, hi + 1) == c
+    bits = mask_bits(m, nb)
+    assert int(bits.sum()) == c
+    for j in np.random.default_rng(0x5EED).integers(0, nb, 4096):
+        assert bool(bits[j]) == is_prime_mr(3 + 2 * (g0 + int(j))), (name, 3 + 2 * (g0 + int(j)))
+    return g0, nb, bits
+
+
+@pytest.mark.parametrize("name", ["from0", "1e13", "1e15", "1e18"])
+def test_mask_window_vs_fast_sieve(oracle, name):
+    g0, nb, bits = _mask_window_case(oracle, name)
+    if name == "from0":  # 3, 5, 7, 9, 11, 13, 15, ...: the sieving primes themselves stay set
+        assert bits[:8].tolist() == [True, True, True, False, True, True, False, True]
+
+
+@pytest.mark.slow
+def test_mask_window_at_the_top_vs_fast_sieve(oracle):
+    """The range ending at index 2^61 - 2 (value 2^62 - 1). The base primes to
+    2^31 - 1 take about 20 s on one thread (once per process: the oracle keeps
+    them): slow."""
+    g0, nb, _ = _mask_window_case(oracle, "top")
+    assert 3 + 2 * (g0 + nb - 1) == 2**62 - 1
+
+
+@pytest.mark.parametrize("name", ["from0", "1e13", "1e15"])
+def test_mask_window_independent_of_thread_count(oracle, name):
+    """A thread's slice is ceil(nbits / threads) rounded up to 64 bits: 1, 3
+    and 8 threads cut the range in different places (with 8, the last slices
+    of the ragged ranges are short or empty) and give the same words."""
+    g0, nb = _MW[name]
+    m1, c1 = oracle.mask_window(g0, nb, threads=1)
+    for t in (3, 8):
+        m, c = oracle.mask_window(g0, nb, threads=t)
+        assert np.array_equal(m, m1) and c == c1, (name, t)
+    assert oracle.mask_window(g0, nb, want_mask=False, threads=3)[1] == c1
+
+
+def test_golden_max_pass_entries():
+    """tests/golden/max_pass.json (make_golden.py --maxpass; tests/test_gpu_max_pass.py
+    and the max_top case of tests/test_gpu_top_of_range.py): the bench window,
+    8,192 + 131 segments from a ragged start at 1e18 and at 1e15 and 8,192 +
+    2,049 ending at 2^62 - 1; the window's count is the golden one of
+    fast_count_window. The planner's formulas (max_pass_ref.planned_passes) give
+    a pass of 8,192 segments, and the dynamic-LDS opt-in, at 1e15 only."""
+    import max_pass_ref as R
+    from max_pass_ref import FIX, MAX_PASS, SEG
+    t = FIX["max_top"]
+    assert 3 + 2 * (t["g0"] + t["nb"] - 1) == 2**62 - 1 and t["nb"] == (MAX_PASS + 2048) * SEG + 777
+    assert t["band1_entries"] > 2**30 > t["first_pass_band1_entries"] > 2**29
+    assert GOLDEN["big"]["window_1e18"]["count"] == FIX["window_1e18"]["count"]
+    w, m = FIX["window_1e18"], FIX["max_1e18"]
+    assert (3 + 2 * w["g0"], 3 + 2 * (w["g0"] + w["nb"] - 1)) == (10**18 + 1, 10**18 + 10**10 - 1)
+    assert w["count"] == 241_272_176 and len(w["segment_counts"]) == -(-w["nb"] // SEG) == 2544
+    assert m["g0"] == (10**18 + 1 - 3) // 2 + 12345 and m["g0"] % 15 and m["g0"] % 64
+    assert m["nb"] == MAX_PASS * SEG + 130 * SEG + 777 and len(m["segment_counts"]) == MAX_PASS + 131
+    f = FIX["max_1e15"]
+    assert f["g0"] == 10**15 // 2 + 12345 and f["nb"] == m["nb"] and f["g0"] % 15 and f["g0"] % 64
+    assert (f["bucket_lo_log2"], f["bucket_split_log2"], f["band0_entries"]) == (20, 20, 0)
+    assert f["first_pass_band1_entries"] > 2**30
+    assert [p[0] for p in R.planned_passes(m["g0"], m["nb"])] == [4096, 4227]
+    assert [p[0] for p in R.planned_passes(t["g0"], t["nb"])] == [4096, 3072, 3073]
+    assert [(p[0], p[3]) for p in R.planned_passes(f["g0"], f["nb"], lo_log2=20, split_log2=20)] == \
+        [(MAX_PASS, 66_816), (131, 2088)]
+    for e in (w, m, t, f):
+        assert sum(e["segment_counts"]) == e["count"] and len(e["piece_sha256"]) == -(-len(e["segment_counts"]) // 128)
+        assert len(e["segment_counts"]) == -(-e["nb"] // SEG) and "Miller-Rabin" in e["source"]
+        assert e["band0_entries"] >= e["first_pass_band0_entries"] >= 0 and e["band1_entries"] >= e["first_pass_band1_entries"] > 0
+        assert (e["first_pass_band0_entries"] > 0) == (e["bucket_split_log2"] > e["bucket_lo_log2"])
+    assert R.stage_lds_bytes(7936) == 64_728 <= R.LDS_OPT_IN < R.stage_lds_bytes(7937) == 65_772
+    assert R.stage_lds_bytes(MAX_PASS) == 4 * (64 + 4 * 64 * 65) == 66_816

@@ -39,6 +39,21 @@ def test_bucket_entries_small_window():
     assert work.bucket_entries_for_range(g0, nb) == want
 
 
+def test_bucket_entries_by_band():
+    """The two bands of bucket_band_entries_for_range against enumeration, with
+    the split inside the range's primes (2^19 < 2^20 < sqrt(1e13) = 3.16e6) and
+    with the production split above them all; the bands add up to the total."""
+    lo = 10**13 + 12345
+    g0, nb = (lo - 3) // 2, 150_000
+    va, vb = 3 + 2 * g0, 3 + 2 * (g0 + nb - 1)
+    b0 = _brute_wheel_marks(va, vb, work.BUCKET_LO, 2**20)
+    b1 = _brute_wheel_marks(va, vb, 2**20, math.isqrt(vb))
+    assert b0 > 0 and b1 > 0
+    assert work.bucket_band_entries_for_range(g0, nb, split=2**20) == (b0, b1)
+    assert work.bucket_band_entries_for_range(g0, nb) == (b0 + b1, 0)
+    assert work.bucket_entries_for_range(g0, nb) == b0 + b1
+
+
 def test_window_bucket_entries_constant():
     """WINDOW_BUCKET_ENTRIES against the Mertens estimate 1e10 * 8/30 *
     (ln ln 1e9 - ln ln 2^19) (within 2%); tools/window_entries.py recomputes it
