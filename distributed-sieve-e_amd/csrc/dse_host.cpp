@@ -533,6 +533,7 @@ const struct {
     {"goldbach_grid", 0, (int64_t)kGbMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->goldbach_grid = (uint32_t)v; }},
     {"race_grid", 0, (int64_t)kRaceMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->race_grid = (uint32_t)v; }},
     {"gaps_grid", 0, (int64_t)kGapsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->gaps_grid = (uint32_t)v; }},
+    {"sums_grid", 0, (int64_t)kSumsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->sums_grid = (uint32_t)v; }},
 };
 
 }  // namespace
@@ -647,6 +648,7 @@ void dse_destroy(dse_ctx* ctx) {
     (void)free_scratch(&d.goldbach_scratch);
     (void)free_scratch(&d.race_scratch);
     (void)free_scratch(&d.gaps_scratch);
+    (void)free_scratch(&d.sums_scratch);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }
@@ -926,6 +928,8 @@ int32_t dse_debug_get_stat(dse_ctx* ctx, const char* name, int64_t* value) {
   } else if (n == "stats_tile_bits") {
     *value = (int64_t)kMaskTileBits;
   } else if (n == "gaps_tile_bits") {
+    *value = (int64_t)kMaskTileBits;
+  } else if (n == "sums_tile_bits") {
     *value = (int64_t)kMaskTileBits;
   } else if (n == "query_index_builds") {
     *value = ctx->query_index_builds;

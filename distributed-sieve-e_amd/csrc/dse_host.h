@@ -3,7 +3,7 @@
 // primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
 // dse_stats_host.cpp: statistics of a mask; dse_query_host.cpp: rank and
 // select; dse_goldbach_host.cpp: minimal Goldbach partitions; dse_race_host.cpp: residue classes
-// and races; dse_tuples_host.cpp: constellations as numbers; dse_gaps_host.cpp: where the gaps are): contexts, device state, the slab
+// and races; dse_tuples_host.cpp: constellations as numbers; dse_gaps_host.cpp: where the gaps are; dse_sums_host.cpp: power and reciprocal sums): contexts, device state, the slab
 // pipe, and the result pass over resident chunks. Not installed; include/dse.h is the ABI.
 #pragma once
 #include <rccl/rccl.h>
@@ -73,6 +73,7 @@ struct DevState {
   StreamScratch goldbach_scratch; // Goldbach partitions (dse_goldbach.hip): the workgroups' slabs, results on their way to the host, a neighbour chunk's tail
   StreamScratch race_scratch; // residue classes and races (dse_race.hip): the workgroups' slabs, results on their way to the host
   StreamScratch gaps_scratch; // where the gaps are (dse_gaps.hip): the workgroups' slabs, results on their way to the host
+  StreamScratch sums_scratch; // power and reciprocal sums (dse_sums.hip): the workgroups' slabs, results on their way to the host, a neighbour chunk's head words
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
 };
 
@@ -111,6 +112,7 @@ struct dse_ctx {
   uint32_t goldbach_grid = 0;  // test-only: > 0 caps the workgroups of a Goldbach launch
   uint32_t race_grid = 0;  // test-only: > 0 caps the workgroups of a race launch
   uint32_t gaps_grid = 0;  // test-only: > 0 caps the workgroups of a gaps launch
+  uint32_t sums_grid = 0;  // test-only: > 0 caps the workgroups of a sums launch
   int64_t query_index_builds = 0;  // rank indices built for resident chunks (dse_debug_get_stat)
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:
@@ -198,6 +200,17 @@ int32_t resident_reduce(dse_ctx* ctx, int32_t k0, int32_t k1, StreamScratch DevS
   *out = acc;
   return DSE_OK;
 }
+// The pattern and `above` rules of the units that match a pattern against the visible candidates
+// (dse_tuples_host.cpp, dse_sums_host.cpp): DSE_EINVAL as dse_tuples_dev_async documents them.
+int32_t tuples_check_pattern(uint32_t require, uint32_t forbid);
+int32_t tuples_check_above(const uint64_t* above, uint32_t above_shift, uint32_t above_bits);
+// Resident chunk k < P sees the first 31 candidates of chunk k + 1 as p's `above`: a pointer into
+// that mask when both are on device d, otherwise its first word copied to head_slot (device memory
+// of d's) on d.stream. resident_above_check: DSE_EINVAL for chunks shorter than that when a chunk
+// from k0 on has a successor. (dse_tuples_host.cpp)
+int32_t resident_above_check(dse_ctx* ctx, int32_t k0);
+int32_t resident_above(dse_ctx* ctx, DevState& d, int32_t k, uint64_t* head_slot, TuplePattern* p);
+
 // The slab pipe (d.pipe; dse_host.cpp), the device current. ensure_slab_pipe: its stream, events,
 // totals and four buffers of min(max(want, 1 MiB), 64 MiB) bytes each, no slot pending.
 int32_t ensure_slab_pipe(DevState& d, uint64_t want);

@@ -5,7 +5,8 @@
 // with one slab of plain stores: scalars of the unit's own, the number of histogram
 // bins it filled (word kSlBins) and those bins (from word kSlHist). Closing launch:
 // one workgroup per kSlabCloseBins bins sums them over the slabs (dse_gaps.hip: takes their minimum); workgroup 0 also
-// reduces the scalars, one slab per thread. The launches are the only ordering.
+// reduces the scalars, one slab per thread. dse_sums.hip has no bins: its slabs hold multi-limb integers, which its one
+// closing workgroup adds with slab_add_limbs / slab_fold_limbs. The launches are the only ordering.
 // Slab and result layouts and the per-word bodies stay with each unit; so do the
 // main kernels' flush of their register counters and slab stores, which a helper
 // here compiled to another instruction stream (profiles/r14/slab_layer_codegen.txt).
@@ -80,6 +81,32 @@ __device__ __forceinline__ void slab_min_bins(const unsigned long long* slabs, u
     if (bin < sl[kSlBins]) acc = min(acc, (uint64_t)sl[kSlHist + bin]);
   }
   if (acc != ~0ull) atomicMin(&s_bins[lane], (unsigned long long)acc);
+}
+
+// The sum over a workgroup of one multi-limb integer per thread (kLimbs little-endian uint64 limbs;
+// dse_sums.hip: a thread's register accumulators in the main kernel, a slab's column in the closing
+// one). Every limb goes as two 32-bit halves, each summed per wave and added to s_half[2 kLimbs],
+// which the caller zeroes and fences with barriers of its own: a sum of 1024 halves stays below 2^42,
+// so the order of the additions cannot matter. slab_fold_limbs then carries the halves into limbs.
+template <uint32_t kLimbs>
+__device__ __forceinline__ void slab_add_limbs(const uint64_t (&x)[kLimbs], unsigned long long* s_half) {
+#pragma unroll
+  for (uint32_t k = 0; k < 2 * kLimbs; ++k) {
+    const uint64_t h = (k & 1u) ? x[k >> 1] >> 32 : x[k >> 1] & 0xFFFFFFFFull;
+    const uint64_t r = wave_sum(h);
+    if ((threadIdx.x & 63u) == 0 && r) atomicAdd(&s_half[k], (unsigned long long)r);
+  }
+}
+template <uint32_t kLimbs>
+__host__ __device__ __forceinline__ void slab_fold_limbs(const unsigned long long* s_half, uint64_t (&out)[kLimbs]) {
+  uint64_t c = 0;  // what the halves below carry into this one: below 2^11
+#pragma unroll
+  for (uint32_t k = 0; k < kLimbs; ++k) {
+    const uint64_t lo = s_half[2 * k] + c;
+    const uint64_t hi = s_half[2 * k + 1] + (lo >> 32);
+    out[k] = (lo & 0xFFFFFFFFull) | (hi << 32);
+    c = hi >> 32;
+  }
 }
 
 // the main launch unless the range is empty, then the closing launch over `bins` histogram bins

@@ -13,21 +13,46 @@
 
 using namespace dse;
 
-namespace {
-
-int32_t tuples_check_pattern(uint32_t require, uint32_t forbid) {
+int32_t dse::tuples_check_pattern(uint32_t require, uint32_t forbid) {
   if (!(require & 1u)) return fail(DSE_EINVAL, "require has bit 0 clear");
   if (require & forbid) return fail(DSE_EINVAL, "require and forbid share a bit");
   return DSE_OK;
 }
 
-int32_t tuples_check_above(const uint64_t* above, uint32_t above_shift, uint32_t above_bits) {
+int32_t dse::tuples_check_above(const uint64_t* above, uint32_t above_shift, uint32_t above_bits) {
   if (above_bits > kTuplesMaxAbove) return fail(DSE_EINVAL, "above_bits above 31");
   if (above_shift > 63) return fail(DSE_EINVAL, "above_shift above 63");
   if (above_bits && !above) return fail(DSE_EINVAL, "null above with above_bits > 0");
   if (above_bits && (reinterpret_cast<uintptr_t>(above) & 7u)) return fail(DSE_EINVAL, "above is not 8-byte aligned");
   return DSE_OK;
 }
+
+int32_t dse::resident_above_check(dse_ctx* ctx, int32_t k0) {
+  const ResidentSet& r = ctx->resident;
+  if (k0 < r.P && (uint64_t)r.cs < kTuplesMaxAbove)
+    return fail(DSE_EINVAL, "chunks of " + std::to_string(r.cs) + " candidates are shorter than the 31 a chunk sees of the next");
+  return DSE_OK;
+}
+
+int32_t dse::resident_above(dse_ctx* ctx, DevState& d, int32_t k, uint64_t* head_slot, TuplePattern* p) {
+  const ResidentSet& r = ctx->resident;
+  const size_t nd = ctx->devs.size();
+  const DevState& nd_dev = ctx->devs[(size_t)k % nd];
+  const uint64_t* const head = r.masks[k].as<uint64_t>();
+  p->above_shift = 0;
+  p->above_bits = kTuplesMaxAbove;
+  if (&nd_dev == &d) {
+    p->above = head;  // the neighbour's mask is this device's: a pointer into it
+  } else {
+    // its first word into this device's scratch, on this device's stream
+    HIP_TRY(nd_dev.device == d.device ? hipMemcpyAsync(head_slot, head, 8, hipMemcpyDeviceToDevice, d.stream)
+                                      : hipMemcpyPeerAsync(head_slot, d.device, head, nd_dev.device, 8, d.stream));
+    p->above = head_slot;
+  }
+  return DSE_OK;
+}
+
+namespace {
 
 // the two launches on a mask that is ready in the stream's order
 RankSource tuples_source(uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev, const TuplePattern& p) {
@@ -105,8 +130,7 @@ extern "C" int32_t dse_tuples_resident(dse_ctx* ctx, int32_t my_num, uint32_t re
   const uint64_t cs = (uint64_t)r.cs;
   if (!cs) return DSE_OK;
   // chunk k < P sees the first 31 candidates of chunk k + 1
-  if (k0 < r.P && cs < kTuplesMaxAbove)
-    return fail(DSE_EINVAL, "chunks of " + std::to_string(cs) + " candidates are shorter than the 31 a chunk sees of the next");
+  if ((rc = resident_above_check(ctx, k0))) return rc;
 
   const size_t nd = ctx->devs.size(), nc = (size_t)(k1 - k0 + 1);
   const uint64_t sum_bytes = primes_scratch_bytes(cs);
@@ -133,20 +157,8 @@ extern "C" int32_t dse_tuples_resident(dse_ctx* ctx, int32_t my_num, uint32_t re
       for (uint32_t j = 0; j < cnt; ++j) {
         const int32_t k = chunks[i][j];
         TuplePattern p{require, forbid, nullptr, 0, 0};
-        if (k < r.P) {
-          const DevState& nd_dev = ctx->devs[(size_t)k % nd];
-          const uint64_t* const head = r.masks[k].as<uint64_t>();
-          p.above_bits = kTuplesMaxAbove;
-          if (&nd_dev == &d) {
-            p.above = head;  // the neighbour's mask is this device's: a pointer into it
-          } else {
-            // its first word into this device's scratch, on this device's stream
-            HIP_TRY(nd_dev.device == d.device
-                        ? hipMemcpyAsync(heads + j, head, 8, hipMemcpyDeviceToDevice, d.stream)
-                        : hipMemcpyPeerAsync(heads + j, d.device, head, nd_dev.device, 8, d.stream));
-            p.above = heads + j;
-          }
-        }
+        if (k < r.P)
+          if (int32_t rv = resident_above(ctx, d, k, heads + j, &p)) return rv;
         const size_t c = (size_t)(k - k0);
         void* const s = static_cast<char*>(d.primes_sums.buf.ptr) + j * sum_bytes;
         src[c] = tuples_source((uint64_t)(k - 1) * cs, cs, r.masks[k - 1].as<uint64_t>(), p);

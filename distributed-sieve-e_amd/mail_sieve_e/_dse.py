@@ -40,6 +40,9 @@ RACE_MAX_MODULUS, RACE_WORDS, RACE_NONE = 64, 17 + 64, (1 << 64) - 1
 # include/dse.h dse_gaps as uint64 words: 9 scalar members, then first[1024]
 GAPS_BINS, GAPS_WORDS, GAPS_NONE = 1024, 9 + 1024, (1 << 64) - 1
 
+# include/dse.h dse_sums as uint64 words, DSE_SUMS_*
+SUMS_WORDS, SUMS_NONE, SUMS_POWER, SUMS_RECIP, SUMS_RECIP_SHIFT = 17, (1 << 64) - 1, 1, 2, 126
+
 # include/dse.h DSE_QUERY_*
 QUERY_NONE = (1 << 64) - 1
 QUERY_RANK, QUERY_SELECT, QUERY_NEXT, QUERY_PREV, QUERY_TEST = range(5)
@@ -110,6 +113,12 @@ SIGNATURES = {
     "dse_gaps_resident": (_i32, [_vp, _i32, _pu64]),
     "dse_gaps_merge": (_i32, [_pu64, _pu64, _pu64]),
     "dse_gaps_records": (_i32, [_pu64, _pu32, _u32, _pu32]),
+    "dse_sums_dev_async": (_i32, [_vp, _u64, _u64, _vp, _u32, _u32, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "dse_sums_range": (_i32, [_vp, _u64, _u64, _u32, _u32, _u32, _pu64]),
+    "dse_sums_resident": (_i32, [_vp, _i32, _u32, _u32, _u32, _pu64]),
+    "dse_sums_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_debug_sums_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _pu64, _u32, _u32, _u32, _pu64]),
+    "dse_debug_sums_recip": (_i32, [_pu64, _u64, _pu64]),
     "dse_debug_gaps_host": (_i32, [_pu64, _u64, _u64, _pu64]),
     "dse_debug_tuples_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _pu64, _u32, _u32, _u64, _pu64, _u64, _pu64]),
     "dse_debug_race_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _u32, _i64, _pu64]),

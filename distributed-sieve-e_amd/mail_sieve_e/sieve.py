@@ -246,6 +246,101 @@ def gaps_host(mask: np.ndarray, g_start: int, nbits: int) -> Gaps:
     return Gaps(out)
 
 
+class Sums:
+    """One dse_sums (include/dse.h "power and reciprocal sums"): the matches of a
+    pattern in the odd candidates [g_start, g_start + nbits), the sum of their values
+    and of the squares, and the fixed-point sum of the reciprocals of their required
+    members, all exact integers. ``words`` is the struct as its uint64 words."""
+
+    def __init__(self, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.shape != (_dse.SUMS_WORDS,):
+            raise ValueError("a dse_sums is %d uint64 words" % _dse.SUMS_WORDS)
+        self.words = w
+
+    @staticmethod
+    def _opt(v):
+        return None if v == _dse.SUMS_NONE else v
+
+    def _limbs(self, at: int, n: int) -> int:
+        return sum(int(self.words[at + k]) << (64 * k) for k in range(n))
+
+    g_start = property(lambda s: int(s.words[0]))
+    nbits = property(lambda s: int(s.words[1]))
+    require = property(lambda s: int(s.words[2]))
+    forbid = property(lambda s: int(s.words[3]))
+    above_bits = property(lambda s: int(s.words[4]))
+    flags = property(lambda s: int(s.words[5]))
+    matches = property(lambda s: int(s.words[6]))
+    first_g = property(lambda s: Sums._opt(int(s.words[7])))
+    last_g = property(lambda s: Sums._opt(int(s.words[8])))
+    sum1 = property(lambda s: s._limbs(9, 2), doc="the sum of the matches' values (0 without SUMS_POWER)")
+    sum2 = property(lambda s: s._limbs(11, 3), doc="the sum of their squares (0 without SUMS_POWER)")
+    recip = property(lambda s: s._limbs(14, 3),
+                     doc="the sum of floor(2^126 / member) over the required members (0 without SUMS_RECIP)")
+
+    @property
+    def first(self) -> Optional[int]:
+        """The value of the lowest match (its lowest member), or None."""
+        return None if self.first_g is None else 3 + 2 * self.first_g
+
+    @property
+    def last(self) -> Optional[int]:
+        return None if self.last_g is None else 3 + 2 * self.last_g
+
+    def reciprocal_bounds(self):
+        """(lo, hi) as fractions.Fraction: the true sum of the reciprocals of the
+        required members lies in [lo, hi]; every floor loses less than 1."""
+        from fractions import Fraction
+        one = 1 << _dse.SUMS_RECIP_SHIFT
+        return (Fraction(self.recip, one),
+                Fraction(self.recip + self.matches * bin(self.require).count("1"), one))
+
+    @property
+    def reciprocal(self) -> float:
+        """The sum of the reciprocals as a float (the lower bound, rounded)."""
+        return self.recip / (1 << _dse.SUMS_RECIP_SHIFT)
+
+    def merge(self, other: "Sums") -> "Sums":
+        """The sums of this range followed by the adjacent ``other`` (dse_sums_merge)."""
+        out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
+        check(lib().dse_sums_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_sums_merge")
+        return Sums(out)
+
+    def __eq__(self, other):
+        return isinstance(other, Sums) and np.array_equal(self.words, other.words)
+
+    def __repr__(self):
+        return (f"Sums(g_start={self.g_start}, nbits={self.nbits}, require={self.require:#x}, forbid={self.forbid:#x}, "
+                f"flags={self.flags}, matches={self.matches}, sum1={self.sum1}, sum2={self.sum2}, "
+                f"reciprocal={self.reciprocal!r})")
+
+
+def sums_host(mask: np.ndarray, g_start: int, nbits: int, require: int = 1, forbid: int = 0,
+              above: Optional[np.ndarray] = None, above_shift: int = 0, above_bits: int = 0,
+              flags: int = _dse.SUMS_POWER | _dse.SUMS_RECIP) -> Sums:
+    """Test-only: the sums kernels' per-word and per-entry bodies run on the host over
+    a host mask and a host ``above`` (include/dse.h dse_debug_sums_host)."""
+    out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    a = None if above is None else np.ascontiguousarray(above, dtype=np.uint64)
+    check(lib().dse_debug_sums_host(u64p(m) if len(m) else None, g_start, nbits, require, forbid,
+                                    u64p(a) if a is not None and len(a) else None, above_shift, above_bits, flags,
+                                    u64p(out)), "dse_debug_sums_host")
+    return Sums(out)
+
+
+def sums_recip_host(values) -> List[int]:
+    """Test-only: floor(2^126 / v) for every v by the sums kernels' division routine,
+    run on the host (include/dse.h dse_debug_sums_recip)."""
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    out = np.zeros(2 * len(v), dtype=np.uint64)
+    check(lib().dse_debug_sums_recip(u64p(v) if len(v) else None, len(v), u64p(out) if len(v) else None),
+          "dse_debug_sums_recip")
+    lo, hi = out[0::2].tolist(), out[1::2].tolist()
+    return [l | h << 64 for l, h in zip(lo, hi)]
+
+
 class Goldbach:
     """One dse_goldbach (include/dse.h "additive questions"): the minimal Goldbach
     partitions of the evens 6 + 2c of the odd candidates [g_start, g_start +
@@ -641,6 +736,47 @@ class Context:
             return self.gaps_range(min((a - 3) // 2, 1 << 62), 0)
         b = hi if hi & 1 else hi - 1
         return self.gaps_range((a - 3) // 2, (b - a) // 2 + 1)
+
+    # -- power and reciprocal sums ----------------------------------------------------
+    def sums_dev_async(self, g_start: int, nbits: int, mask_ptr: int, require: int, forbid: int, above_ptr: int,
+                       above_shift: int, above_bits: int, flags: int, out_ptr: int, stream_ptr: int = 0):
+        """The sums over the matches of (require, forbid) in the device mask as one
+        dse_sums (_dse.SUMS_WORDS uint64 words) in device memory at out_ptr; the
+        above_bits candidates behind the range are the bits from above_shift on of the
+        device bit string at above_ptr (include/dse.h dse_sums_dev_async)."""
+        check(lib().dse_sums_dev_async(self.ptr, g_start, nbits, mask_ptr or None, require, forbid,
+                                       above_ptr or None, above_shift, above_bits, flags, out_ptr or None,
+                                       stream_ptr or None),
+              "dse_sums_dev_async")
+
+    def sums_range(self, g_start: int, nbits: int, require: int = 1, forbid: int = 0,
+                   flags: int = _dse.SUMS_POWER | _dse.SUMS_RECIP) -> Sums:
+        """gen-table + sieve-e of an odd-index range (and of the 31 candidates above
+        it) and the sums over its matches of (require, forbid), computed on the
+        device: only the dse_sums reaches the host."""
+        out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
+        check(lib().dse_sums_range(self.ptr, g_start, nbits, require, forbid, flags, u64p(out)), "dse_sums_range")
+        return Sums(out)
+
+    def sums_resident(self, my_num: Optional[int] = None, require: int = 1, forbid: int = 0,
+                      flags: int = _dse.SUMS_POWER | _dse.SUMS_RECIP) -> Sums:
+        """The sums of a chunk the last sieve_all left on its device, or (my_num=None)
+        of all its chunks: the per-chunk results merged in order."""
+        out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
+        check(lib().dse_sums_resident(self.ptr, 0 if my_num is None else my_num, require, forbid, flags, u64p(out)),
+              "dse_sums_resident")
+        return Sums(out)
+
+    def sums_window(self, lo: int, hi: int, require: int = 1, forbid: int = 0,
+                    flags: int = _dse.SUMS_POWER | _dse.SUMS_RECIP) -> Sums:
+        """The sums over the matches whose lowest member is an odd value in
+        [max(lo, 3), hi] (primes_window's convention); an empty window gives the
+        empty result."""
+        a = max(lo, 3) | 1
+        if hi < a:
+            return self.sums_range(min((a - 3) // 2, 1 << 62), 0, require, forbid, flags)
+        b = hi if hi & 1 else hi - 1
+        return self.sums_range((a - 3) // 2, (b - a) // 2 + 1, require, forbid, flags)
 
     # -- constellations as numbers -------------------------------------------------
     def tuples_dev_async(self, g_start: int, nbits: int, mask_ptr: int, require: int, forbid: int, above_ptr: int,

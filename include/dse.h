@@ -691,6 +691,89 @@ int32_t dse_gaps_merge(const dse_gaps *a, const dse_gaps *b, dse_gaps *out);
  * DSE_EINVAL for a null g or count, or a null d_out with cap > 0. */
 int32_t dse_gaps_records(const dse_gaps *g, uint32_t *d_out, uint32_t cap, uint32_t *count);
 
+/* ---- power and reciprocal sums ----------------------------------------------- */
+
+/* Sums over the matches of a pattern in a device-resident mask, computed on the GPU in one read of
+ * the mask; only the dse_sums crosses to the host: the sum of the primes (A046731 less the prime 2),
+ * of their squares, of their reciprocals (Mertens), and Brun-type sums over constellations such as
+ * B2 = sum of 1/p + 1/(p + 2) over the twins. Candidates, entries, values and g are dse_stats'. The
+ * pattern (require, forbid), the visible candidates (above / above_shift / above_bits <= 31) and
+ * the match rule are exactly dse_tuples': a match belongs to the range that holds its lowest member,
+ * so adjacent ranges that each see the next one's head count every match of their union once.
+ * require = 1, forbid = 0 sums over the primes, require = 3 over the twins, require = 1 | 1 << d with
+ * forbid = the bits 1 .. d - 1 over the consecutive primes exactly 2d apart.
+ *
+ * The value of a match at position i is v = 3 + 2 (g_start + i), its lowest member, as dse_tuples
+ * reports it. Every sum is an exact integer in little-endian uint64 limbs, so a result does not
+ * depend on the order of the additions and dse_sums_merge is plain addition:
+ *   sum1  = sum of v, sum2 = sum of v^2 (flag DSE_SUMS_POWER, else 0);
+ *   recip = sum over the matches, over every set bit j of require, of floor(2^126 / (v + 2j))
+ *           (flag DSE_SUMS_RECIP, else 0): the fixed-point sum of the reciprocals of all required
+ *           members, the convention of Brun-type constants: 1/5 counts in (3, 5) and in (5, 7).
+ *           With require = 1 it is the sum of floor(2^126 / p).
+ * matches, first_g and last_g are always written.
+ *
+ * Bounds. v >= 3, so a term is below 2^125. The sum of 1/v over all odd v < 2^62 is under 23, which
+ * with 32 members gives recip < 23 * 32 * 2^126 < 2^141. The sieve's values are below 2^62 and there
+ * are fewer than 2^61 of them, so sum1 < 2^123 and sum2 < 2^61 * 2^124 = 2^185. A caller's mask may
+ * reach the odd-index bound 2^62 (values below 2^63 + 2, 2^62 candidates): then sum1 < 2^126,
+ * sum2 < 2^189 and the reciprocals still sum to less than 24. No limb can overflow, even after
+ * merging the whole accepted range. Every floor loses less than 1, so the true sum of the
+ * reciprocals lies in [recip / 2^126, (recip + matches * popcount(require)) / 2^126].
+ *
+ * Every member is a uint64_t and there is no padding: bindings may treat a dse_sums as an array of
+ * DSE_SUMS_WORDS uint64 words. */
+#define DSE_SUMS_POWER 1u /* sum1, sum2 */
+#define DSE_SUMS_RECIP 2u /* recip */
+#define DSE_SUMS_NONE UINT64_MAX
+#define DSE_SUMS_RECIP_SHIFT 126
+#define DSE_SUMS_WORDS 17
+typedef struct dse_sums {
+  uint64_t g_start, nbits;                     /* the range the numbers are of */
+  uint64_t require, forbid, above_bits, flags; /* what the numbers are of */
+  uint64_t matches;                            /* always */
+  uint64_t first_g, last_g; /* g of the lowest / highest match, DSE_SUMS_NONE if none; always */
+  uint64_t sum1[2];         /* sum of v,   128 bits, little-endian limbs; 0 without POWER */
+  uint64_t sum2[3];         /* sum of v^2, 192 bits;                     0 without POWER */
+  uint64_t recip[3]; /* sum over matches, over every set bit j of require, of floor(2^126 / (v + 2j)), 192 bits; 0 without RECIP */
+} dse_sums;
+
+/* Async on stream, on a caller-owned device mask. out_dev: sizeof(dse_sums) bytes of device memory,
+ * 8-byte aligned; every member is written and nothing outside it is touched. flags: any of
+ * DSE_SUMS_POWER | DSE_SUMS_RECIP; 0 gives the count and the positions only. Bits past nbits in the
+ * last mask word are ignored; nbits = 0 writes the empty result (0 matches, NONE, zero sums).
+ * DSE_EINVAL for a null ctx or out_dev, a null mask with nbits > 0, a misaligned out_dev, flags with
+ * unknown bits, require with bit 0 clear, require & forbid != 0, above_bits > 31, above_shift > 63,
+ * or a null or misaligned above_dev with above_bits > 0. DSE_ERANGE for visible candidates beyond
+ * 2^62 or more than 2^44 candidates in one call. */
+int32_t dse_sums_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, const uint64_t *mask_dev,
+                           uint32_t require, uint32_t forbid, const uint64_t *above_dev,
+                           uint32_t above_shift, uint32_t above_bits, uint32_t flags,
+                           dse_sums *out_dev, void *stream);
+
+/* gen-table + sieve-e + the sums of an odd-index range, on the first device; host result. The range
+ * is sieved together with the candidates above it in one scratch mask (31 of them, fewer where the
+ * 2^62 bound ends them), which are its `above`, as dse_tuples_range does. */
+int32_t dse_sums_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, uint32_t require,
+                       uint32_t forbid, uint32_t flags, dse_sums *out);
+
+/* The sums of chunk my_num left resident by the last dse_sieve_all; my_num = 0: of all P chunks, that
+ * is of [3, 3 + 2 P cs) (dse_stats_resident's convention). Chunk k < P sees the first 31 candidates
+ * of chunk k + 1 exactly as dse_tuples_resident arranges it; chunk P has no `above`. For all chunks,
+ * every chunk's launches are enqueued on its own device's stream before any is waited for, and the
+ * P results are merged on the host in chunk order. DSE_EINVAL if the chunk is not resident, or for
+ * chunks of fewer than 31 candidates when a chunk with a successor is asked for. */
+int32_t dse_sums_resident(dse_ctx *ctx, int32_t my_num, uint32_t require, uint32_t forbid,
+                          uint32_t flags, dse_sums *out);
+
+/* The sums of the union of two adjacent ranges, by host arithmetic only; out may alias a or b. Needs
+ * a->g_start + a->nbits == b->g_start, equal require, forbid and flags, and a->above_bits >=
+ * min(span - 1, b->nbits + b->above_bits): a must have seen across the seam (else DSE_EINVAL; out is
+ * not touched). A union that ends above 2^62 gives DSE_ERANGE. matches and the sums add with
+ * carries; first_g / last_g come from whichever side has them; out->above_bits = b->above_bits. The
+ * merge is associative, with empty pieces on either side. */
+int32_t dse_sums_merge(const dse_sums *a, const dse_sums *b, dse_sums *out);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -745,6 +828,9 @@ int32_t dse_gaps_records(const dse_gaps *g, uint32_t *d_out, uint32_t cap, uint3
  *   "gaps_grid" = k in 1..1024: the dse_gaps_* launches use at most k
  *   workgroups, so one workgroup walks several tiles and the closing launch
  *   reduces several slabs on tiny inputs; 0 = default (one resident round).
+ *   "sums_grid" = k in 1..1024: the dse_sums_* launches use at most k
+ *   workgroups, so one workgroup walks several tiles and the closing launch
+ *   adds several slabs on tiny inputs; 0 = default (one resident round).
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -757,6 +843,7 @@ int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
  *   "primes_tile_bits": candidates per tile of the dse_primes_* kernels;
  *   "stats_tile_bits": candidates per tile of the dse_stats_* kernels;
  *   "gaps_tile_bits": candidates per tile of the dse_gaps_* main kernel;
+ *   "sums_tile_bits": candidates per tile of the dse_sums_* main kernels;
  *   "query_index_builds": rank indices dse_query_resident has built for
  *   resident chunks so far (one per chunk and dse_sieve_all that replaced the
  *   masks);
@@ -866,6 +953,20 @@ int32_t dse_debug_race_host(const uint64_t *mask, uint64_t g_start, uint64_t nbi
  * same bits. Test-only; DSE_EINVAL / DSE_ERANGE as dse_gaps_dev_async for the
  * pointers and the range. */
 int32_t dse_debug_gaps_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, dse_gaps *out);
+
+/* The dse_sums_* kernels' own per-word and per-entry bodies, run on the host in a plain loop over
+ * the words of a host mask and a host `above` (no device call), the device's division routine
+ * included (not the compiler's 128-bit divide): the same result as dse_sums_dev_async on the same
+ * bits. Test-only; DSE_EINVAL / DSE_ERANGE as dse_sums_dev_async for the pointers, the pattern,
+ * `above`, the flags and the range. */
+int32_t dse_debug_sums_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, uint32_t require,
+                            uint32_t forbid, const uint64_t *above, uint32_t above_shift,
+                            uint32_t above_bits, uint32_t flags, dse_sums *out);
+
+/* That division routine alone, on the host: out[2i], out[2i + 1] = the low and high word of
+ * floor(2^126 / v[i]), i < n, for any v[i] >= 3. Test-only; DSE_EINVAL for a null pointer with
+ * n > 0, DSE_ERANGE for a v[i] below 3 (nothing is written). */
+int32_t dse_debug_sums_recip(const uint64_t *v, uint64_t n, uint64_t *out);
 
 /* The dse_tuples_* kernels' own per-word body, run on the host in a plain loop over
  * the words of a host mask and a host `above` (no device call): the same totals and
