@@ -101,6 +101,13 @@ constexpr uint32_t kL0 = odd_primes_upto(TB);
 // pl[] word -> p. Bit 31 is not a plan bit: it marks a lane past the table
 // end (load_L), so a plan has at most 11 bits (asserted below).
 constexpr uint32_t kLPrimeMask = 0x800FFFFFu;
+// The unit queue's first claimed position in the instantiations without bucket
+// units: positions below it are pre-assigned, two to each of the workgroup's
+// NT / 64 waves (mark_segment). The bucket instantiation claims every position
+// (0): with its first positions pre-assigned the 1e18 window ran 0.6% slower
+// (profiles/r20/window_parts.txt).
+template <bool BK>
+constexpr uint32_t kFirstClaim = BK ? 0u : 2 * (NT / 64);
 static_assert(kWheelMaxPrime <= (1u << 20), "pl[] words: the L primes (odd, <= kWheelMaxPrime) are below 2^20");
 __host__ __device__ constexpr uint32_t l_plan(uint32_t pmin, uint32_t pmax, uint32_t kp) {
   if (pmin > kp) return 2;
@@ -814,12 +821,22 @@ __device__ __forceinline__ void unit_L(const LargeOps& o, uint64_t Vs, uint64_t 
   }
 }
 
+// floor(sqrt(v)), v < 2^62: the double root is within one of it, and the two
+// loops correct it with exact 64-bit products.
+__device__ __forceinline__ uint32_t isqrt_u64(uint64_t v) {
+  uint32_t r = (uint32_t)__builtin_sqrt((double)v);
+  while ((uint64_t)r * r > v) --r;
+  while ((uint64_t)(r + 1) * (r + 1) <= v) ++r;
+  return r;
+}
+
 struct WheelLdsLow {
   uint64_t mid_m[kMidCap];         // Barrett factors of the staged mid primes
   uint32_t mid_p[kMidCap];         // p | (30^{-1} mod p) << 16
   uint32_t mid_x[kMidCap];         // Vs mod p of this workgroup's segment (MidRes)
   uint32_t mid_inc[kMidCap];       // G W mod p
   uint32_t x_seg;                  // the launch segment mid_x holds (~0: none)
+  uint32_t sq[2];                  // isqrt(Vs), isqrt(Vend - 1) of the workgroup's segment (prepare_segment)
   uint4 itab[kGDW];                // init tables U_G, 4 copies shifted by 0..3 dwords (kGDW / 4 blocks each)
   uint32_t thr[5];
   uint32_t ctr;                    // unit counter
@@ -873,8 +890,10 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     s_thr[3] = min(min(wa.nthr[3], np), s_thr[0] + kMidCap);
     s_thr[2] = min(s_thr[2], s_thr[3]);
     s_thr[4] = max(s_thr[3], min(wa.nthr[4], np));
-    lds.ctr = 0;
-    lds.x_seg = ~0u;
+    if (BK) {  // the other instantiations: prepare_segment
+      lds.ctr = 0;
+      lds.x_seg = ~0u;
+    }
   }
   if (tid < kMaxRanges) lds.rcnt[tid] = 0;
   for (uint32_t idx = tid; idx < 4 * kGDW; idx += NT) reinterpret_cast<uint32_t*>(lds.itab)[idx] = g_init_tables.w[idx];
@@ -908,6 +927,27 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     uint32_t r = 0;
     for (uint32_t i = 1; i < wa.nranges; ++i) r = g >= wa.r[i].seg0 ? i : r;
     return r;
+  };
+  // Without bucket units (the bucket instantiation keeps the round-19 code:
+  // every form of this one tried there raised its SGPR spills from 58 to 59 or
+  // more, and it gained nothing on the 1e18 window, profiles/r20/INDEX.md).
+  // What thread 0 leaves in LDS for the workgroup's segment g of round t,
+  // behind a barrier: the unit counter at its first claimed position; whether
+  // mid_x holds this segment's residues; and isqrt(Vs) and isqrt(Vend - 1),
+  // which mark_segment's waves read as two wave-uniform words where every wave
+  // took both roots itself (a double sqrt and two correction loops each, per
+  // wave and segment). p^2 > Vs <=> p > sq[0]; p^2 < Vend <=> p <= sq[1].
+  auto prepare_segment = [&](uint32_t g, uint32_t t) {
+    const uint32_t r = range_of(g);
+    const uint64_t Vs = wa.r[r].V0 + (uint64_t)(g - wa.r[r].seg0) * kWheelSpan;
+    lds.ctr = kFirstClaim<BK>;
+    // the mid units of the workgroup's previous segment left their residues
+    // for this one: valid if that segment was of the same range and every mid
+    // unit ran in it (p^2 < its Vs for p <= TB)
+    const bool same = t > 0 && g - wa.r[r].seg0 >= grid;
+    lds.x_seg = same && Vs - (uint64_t)grid * kWheelSpan >= (uint64_t)TB * TB ? g : ~0u;
+    lds.sq[0] = isqrt_u64(Vs);
+    lds.sq[1] = isqrt_u64(Vs + kWheelSpan - 1);
   };
 
   // ---- init: small-prime patterns (7..61) of segment s into the image. Lane
@@ -1121,14 +1161,10 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     const uint64_t* rho_pack_p = reinterpret_cast<const uint64_t*>(
         (const char*)__builtin_amdgcn_kernarg_segment_ptr() + kWaOffset +
         range_of(g_seg) * sizeof(WheelRange) + offsetof(WheelRange, rho_pack));
-    uint32_t sqrt_vs = (uint32_t)__builtin_sqrt((double)Vs);  // isqrt(Vs) < 2^32 (Vs < 2^64)
-    while ((uint64_t)sqrt_vs * sqrt_vs > Vs) --sqrt_vs;
-    while ((uint64_t)(sqrt_vs + 1) * (sqrt_vs + 1) <= Vs) ++sqrt_vs;
-    sqrt_vs = __builtin_amdgcn_readfirstlane(sqrt_vs);
-    uint32_t sqrt_ve = (uint32_t)__builtin_sqrt((double)(Vend - 1));  // p^2 < Vend <=> p <= isqrt(Vend - 1)
-    while ((uint64_t)sqrt_ve * sqrt_ve > Vend - 1) --sqrt_ve;
-    while ((uint64_t)(sqrt_ve + 1) * (sqrt_ve + 1) <= Vend - 1) ++sqrt_ve;
-    sqrt_ve = __builtin_amdgcn_readfirstlane(sqrt_ve);
+    // isqrt(Vs) and isqrt(Vend - 1) (p^2 < Vend <=> p <= isqrt(Vend - 1)): left
+    // by thread 0 (prepare_segment), or per wave with bucket units
+    const uint32_t sqrt_vs = __builtin_amdgcn_readfirstlane(BK ? isqrt_u64(Vs) : lds.sq[0]);
+    const uint32_t sqrt_ve = __builtin_amdgcn_readfirstlane(BK ? isqrt_u64(Vend - 1) : lds.sq[1]);
     const uint32_t rot = (i_mid1 + lane) & 7;  // = table index & 7 of this lane's large primes
     // absolute residue (q + rot) & 7 at step q: its plane and e bit
     const uint32_t pl_rot = ((rg.pl_pack >> (3 * rot)) | (rg.pl_pack << (24 - 3 * rot))) & 0xFFFFFFu;
@@ -1160,6 +1196,7 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     // on the spot (draining the previous unit's marks with it), which
     // defeats the two-ahead issue. Read through claimed().
     const uint32_t ctr_addr = lds_addr(&lds.ctr);
+    const uint32_t wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto claim = [&]() -> uint32_t {
       uint32_t j = 0;
       if (lane == 0) asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(j) : "v"(ctr_addr), "v"(1u) : "memory");
@@ -1195,12 +1232,16 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
     // loads just issued (a vmcnt(4) and a vmcnt(0) per large unit).
     LargeOps cur, nxt;
     LargeOps cur1, nxt1;  // the unit's second 64 primes
-    uint32_t d_nxt = decode(claimed(claim()));
+    // without bucket units a wave's first two units are queue positions wave
+    // and wave + NT / 64 of every segment (the counter starts at kFirstClaim):
+    // no claim round trips before the first mark; positions past n_q decode to
+    // ~0u as claimed ones do
+    uint32_t d_nxt = decode(BK ? claimed(claim()) : wave_u);
     if ((d_nxt >> 30) == 1) {
       load_L(nxt, PL, M, A, i_mid1 + kLU * (d_nxt & kIdx) + lane, i_big, need_m);
       load_L(nxt1, PL, M, A, i_mid1 + kLU * (d_nxt & kIdx) + 64 + lane, i_big, need_m);
     }
-    uint32_t d_after = decode(claimed(claim()));
+    uint32_t d_after = decode(BK ? claimed(claim()) : wave_u + NT / 64);
     // the first unit's operands landed before the loop (an asm that reads
     // them makes the compiler wait here), so on no path into the loop does a
     // set's register still wait for a load
@@ -1305,27 +1346,36 @@ __global__ __launch_bounds__(NT) void wheel_segments_kernel(const void* __restri
   };
 
   if (T > 0) init_segment(lds.img, blockIdx.x);
-  __syncthreads();
+  if (BK) __syncthreads();
   for (uint32_t t = 0; t < T; ++t) {
     const uint32_t s = blockIdx.x + t * grid;
+    if (!BK) {
+      // thread 0 prepares segment s; the waves still in the expand and init of
+      // the segment before read none of these words
+      if (tid == 0) prepare_segment(s, t);
+      __syncthreads();
+    }
     mark_segment(lds.img, s);
     lds_drain();
-    __syncthreads();
+    __syncthreads();  // every claim of this segment has returned
     expand_segment(lds.img, s);
     // init of this workgroup's next segment, on the rows this wave just
     // expanded: no barrier in between, and waves drift into init while
     // others still expand
     if (t + 1 < T) init_segment(lds.img, s + grid);
-    if (tid == 0) {
-      lds.ctr = 0;  // all claims of this segment returned before the barrier above
-      // the mid units left their residues for segment s + grid: valid if it is
-      // of the same range and every mid unit ran (p^2 < Vs for p <= TB)
-      const uint32_t r0 = range_of(s), r1 = range_of(s + grid);
-      const uint64_t Vs = wa.r[r0].V0 + (uint64_t)(s - wa.r[r0].seg0) * kWheelSpan;
-      lds.x_seg = t + 1 < T && r1 == r0 && Vs >= (uint64_t)TB * TB ? s + grid : ~0u;
+    if (BK) {
+      if (tid == 0) {
+        lds.ctr = 0;
+        // the mid units left their residues for segment s + grid: valid if it is
+        // of the same range and every mid unit ran (p^2 < Vs for p <= TB)
+        const uint32_t r0 = range_of(s), r1 = range_of(s + grid);
+        const uint64_t Vs = wa.r[r0].V0 + (uint64_t)(s - wa.r[r0].seg0) * kWheelSpan;
+        lds.x_seg = t + 1 < T && r1 == r0 && Vs >= (uint64_t)TB * TB ? s + grid : ~0u;
+      }
+      __syncthreads();
     }
-    __syncthreads();
   }
+  if (!BK) __syncthreads();
 
   if (tid < wa.nranges && lds.rcnt[tid]) atomicAdd(wa.r[tid].count, lds.rcnt[tid]);
 }
