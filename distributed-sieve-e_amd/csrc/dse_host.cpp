@@ -534,6 +534,10 @@ const struct {
     {"race_grid", 0, (int64_t)kRaceMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->race_grid = (uint32_t)v; }},
     {"gaps_grid", 0, (int64_t)kGapsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->gaps_grid = (uint32_t)v; }},
     {"sums_grid", 0, (int64_t)kSumsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->sums_grid = (uint32_t)v; }},
+    {"consec_grid", 0, (int64_t)kConsecMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->consec_grid = (uint32_t)v; }},
+    {"consec_flush_tiles", 0, (int64_t)kConsecFlushTiles, "out of range",
+     [](dse_ctx* c, int64_t v) { c->consec_flush_tiles = (uint32_t)v; }},
+    {"consec_body", 0, 2, "must be 0, 1 or 2", [](dse_ctx* c, int64_t v) { c->consec_body = (uint32_t)v; }},
 };
 
 }  // namespace
@@ -649,6 +653,7 @@ void dse_destroy(dse_ctx* ctx) {
     (void)free_scratch(&d.race_scratch);
     (void)free_scratch(&d.gaps_scratch);
     (void)free_scratch(&d.sums_scratch);
+    (void)free_scratch(&d.consec_scratch);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }

@@ -3,7 +3,7 @@
 // primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
 // dse_stats_host.cpp: statistics of a mask; dse_query_host.cpp: rank and
 // select; dse_goldbach_host.cpp: minimal Goldbach partitions; dse_race_host.cpp: residue classes
-// and races; dse_tuples_host.cpp: constellations as numbers; dse_gaps_host.cpp: where the gaps are; dse_sums_host.cpp: power and reciprocal sums): contexts, device state, the slab
+// and races; dse_tuples_host.cpp: constellations as numbers; dse_gaps_host.cpp: where the gaps are; dse_sums_host.cpp: power and reciprocal sums; dse_consec_host.cpp: residue pairs of consecutive primes): contexts, device state, the slab
 // pipe, and the result pass over resident chunks. Not installed; include/dse.h is the ABI.
 #pragma once
 #include <rccl/rccl.h>
@@ -74,6 +74,7 @@ struct DevState {
   StreamScratch race_scratch; // residue classes and races (dse_race.hip): the workgroups' slabs, results on their way to the host
   StreamScratch gaps_scratch; // where the gaps are (dse_gaps.hip): the workgroups' slabs, results on their way to the host
   StreamScratch sums_scratch; // power and reciprocal sums (dse_sums.hip): the workgroups' slabs, results on their way to the host, a neighbour chunk's head words
+  StreamScratch consec_scratch; // residue pairs of consecutive primes (dse_consec.hip): the workgroups' slabs, results on their way to the host
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
 };
 
@@ -113,6 +114,9 @@ struct dse_ctx {
   uint32_t race_grid = 0;  // test-only: > 0 caps the workgroups of a race launch
   uint32_t gaps_grid = 0;  // test-only: > 0 caps the workgroups of a gaps launch
   uint32_t sums_grid = 0;  // test-only: > 0 caps the workgroups of a sums launch
+  uint32_t consec_grid = 0;  // test-only: > 0 caps the workgroups of a consec launch
+  uint32_t consec_flush_tiles = 0;  // test-only: > 0: the tiles after which a consec workgroup empties its 32-bit counters
+  uint32_t consec_body = 0;  // test-only: 1 / 2 force the bit-parallel / per-entry body of the consec main kernel
   int64_t query_index_builds = 0;  // rank indices built for resident chunks (dse_debug_get_stat)
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:

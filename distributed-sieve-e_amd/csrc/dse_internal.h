@@ -1,9 +1,9 @@
 // Internal interface between the gfx950 kernel units (dse_base.hip, dse_wheel.hip,
 // dse_wheel_plain.hip, dse_wheel_half.hip, dse_bucket.hip, dse_finish.hip,
-// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip, dse_race.hip, dse_tuples.hip, dse_gaps.hip, dse_sums.hip, and the test-only dse_arith_probe.hip)
+// dse_primes.hip, dse_stats.hip, dse_query.hip, dse_goldbach.hip, dse_race.hip, dse_tuples.hip, dse_gaps.hip, dse_sums.hip, dse_consec.hip, and the test-only dse_arith_probe.hip)
 // and the C-ABI host layer (dse_host.cpp,
 // dse_finish_host.cpp, dse_primes_host.cpp, dse_stats_host.cpp, dse_query_host.cpp,
-// dse_goldbach_host.cpp, dse_race_host.cpp, dse_tuples_host.cpp, dse_gaps_host.cpp, dse_sums_host.cpp). Not installed;
+// dse_goldbach_host.cpp, dse_race_host.cpp, dse_tuples_host.cpp, dse_gaps_host.cpp, dse_sums_host.cpp, dse_consec_host.cpp). Not installed;
 // include/dse.h is the ABI. The units that read a resident mask (finish,
 // primes, stats, query, goldbach, race, tuples) share its range, tiles and clipped word load (dse_mask.h);
 // every unit with a workgroup sum, scan or best-of takes it from dse_block.h; the two that reduce
@@ -347,6 +347,21 @@ uint32_t gaps_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
 uint64_t gaps_scratch_bytes(uint32_t grid);
 hipError_t launch_gaps(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint64_t* out, void* slabs,
                        uint32_t grid, hipStream_t stream);
+
+// The residue pairs of consecutive primes of a mask (dse_consec.hip): the two launches of a slab
+// reduction (dse_slab.h), which write the dse_consec (kConsecWords uint64 words, dse_consec_word.h) at
+// `out` for the modulus q (3..64). grid = consec_grid(nbits, CUs of the device, cap or 0): slab_grid's
+// rule. slabs: consec_scratch_bytes(grid) bytes of device scratch. flush_tiles: the tiles after which
+// a workgroup empties its 32-bit counters (0: kConsecFlushTiles, the most); body: 0 the in-word body
+// of the measured threshold, 1 the bit-parallel one wherever it is built, 2 the per-entry one.
+constexpr uint32_t kConsecMaxGrid = 1024;
+// A 32-bit bin grows by at most 64 pairs per word and tile (every entry is the upper prime of at most
+// one pair, counted by its word): emptied into 64 bits after at most this many tiles.
+constexpr uint32_t kConsecFlushTiles = 0xFFFFFFFFu / (64u * kMaskTileWords);
+uint32_t consec_grid(uint64_t nbits, int num_cus, uint32_t grid_cap);
+uint64_t consec_scratch_bytes(uint32_t grid);
+hipError_t launch_consec(uint64_t g_start, uint64_t nbits, const uint64_t* mask, uint32_t q, uint64_t* out,
+                         void* slabs, uint32_t grid, uint32_t flush_tiles, uint32_t body, hipStream_t stream);
 
 // Power and reciprocal sums over the matches of a pattern (dse_sums.hip): the two launches of a slab
 // reduction (dse_slab.h), which write the dse_sums (kSumsWords uint64 words) at `out`. The pattern and

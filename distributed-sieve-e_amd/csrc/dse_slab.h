@@ -1,10 +1,11 @@
 // dse_slab.h -- the two-launch slab reduction of the units that turn a whole mask
-// range into one small struct (dse_stats.hip, dse_goldbach.hip, dse_gaps.hip; dse_race.hip puts a
+// range into one small struct (dse_stats.hip, dse_goldbach.hip, dse_gaps.hip, dse_consec.hip; dse_race.hip puts a
 // count launch over the same runs in front). Main launch: `grid`
 // workgroups, each walking its own contiguous run of tiles (dse_mask.h) and ending
 // with one slab of plain stores: scalars of the unit's own, the number of histogram
 // bins it filled (word kSlBins) and those bins (from word kSlHist). Closing launch:
-// one workgroup per kSlabCloseBins bins sums them over the slabs (dse_gaps.hip: takes their minimum); workgroup 0 also
+// one workgroup per kSlabCloseBins bins sums them over the slabs (dse_gaps.hip: takes their minimum; dse_consec.hip:
+// the 64 bins of the row it writes, slab_sum_bins_at); workgroup 0 also
 // reduces the scalars, one slab per thread. dse_sums.hip has no bins: its slabs hold multi-limb integers, which its one
 // closing workgroup adds with slab_add_limbs / slab_fold_limbs. The launches are the only ordering.
 // Slab and result layouts and the per-word bodies stay with each unit; so do the
@@ -57,16 +58,22 @@ __device__ __forceinline__ void slab_tiles(const SlabRun& r, uint64_t& t0, uint6
 
 // The closing kernel's column sum into s_bins[0 .. kSlabCloseBins), which the caller zeroes and
 // fences with barriers of its own: 16 slabs at a time, 512 contiguous bytes of each.
+// slab_sum_bins_at: the bins bin0 .. bin0 + kSlabCloseBins of a workgroup's own choice.
 template <uint32_t kSlabWords, uint32_t kSlBins, uint32_t kSlHist>
-__device__ __forceinline__ void slab_sum_bins(const unsigned long long* slabs, uint32_t nslabs,
-                                              unsigned long long* s_bins) {
-  const uint32_t grp = threadIdx.x >> 6, lane = threadIdx.x & 63u, bin = blockIdx.x * kSlabCloseBins + lane;
+__device__ __forceinline__ void slab_sum_bins_at(const unsigned long long* slabs, uint32_t nslabs, uint32_t bin0,
+                                                 unsigned long long* s_bins) {
+  const uint32_t grp = threadIdx.x >> 6, lane = threadIdx.x & 63u, bin = bin0 + lane;
   uint64_t acc = 0;
   for (uint32_t s = grp; s < nslabs; s += kSlabCloseThreads / 64) {
     const unsigned long long* const sl = slabs + (uint64_t)s * kSlabWords;
     if (bin < sl[kSlBins]) acc += sl[kSlHist + bin];
   }
   if (acc) atomicAdd(&s_bins[lane], (unsigned long long)acc);
+}
+template <uint32_t kSlabWords, uint32_t kSlBins, uint32_t kSlHist>
+__device__ __forceinline__ void slab_sum_bins(const unsigned long long* slabs, uint32_t nslabs,
+                                              unsigned long long* s_bins) {
+  slab_sum_bins_at<kSlabWords, kSlBins, kSlHist>(slabs, nslabs, blockIdx.x * kSlabCloseBins, s_bins);
 }
 
 // The column minimum of a unit whose bins hold positions (~0: none), into s_bins[0 .. kSlabCloseBins),

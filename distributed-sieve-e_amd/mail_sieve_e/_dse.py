@@ -43,6 +43,9 @@ GAPS_BINS, GAPS_WORDS, GAPS_NONE = 1024, 9 + 1024, (1 << 64) - 1
 # include/dse.h dse_sums as uint64 words, DSE_SUMS_*
 SUMS_WORDS, SUMS_NONE, SUMS_POWER, SUMS_RECIP, SUMS_RECIP_SHIFT = 17, (1 << 64) - 1, 1, 2, 126
 
+# include/dse.h dse_consec as uint64 words: 7 scalar members, then counts[64 * 64]
+CONSEC_MAX_MODULUS, CONSEC_WORDS, CONSEC_NONE = 64, 7 + 64 * 64, (1 << 64) - 1
+
 # include/dse.h DSE_QUERY_*
 QUERY_NONE = (1 << 64) - 1
 QUERY_RANK, QUERY_SELECT, QUERY_NEXT, QUERY_PREV, QUERY_TEST = range(5)
@@ -117,6 +120,11 @@ SIGNATURES = {
     "dse_sums_range": (_i32, [_vp, _u64, _u64, _u32, _u32, _u32, _pu64]),
     "dse_sums_resident": (_i32, [_vp, _i32, _u32, _u32, _u32, _pu64]),
     "dse_sums_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_consec_dev_async": (_i32, [_vp, _u64, _u64, _vp, _u32, _vp, _vp]),
+    "dse_consec_range": (_i32, [_vp, _u64, _u64, _u32, _pu64]),
+    "dse_consec_resident": (_i32, [_vp, _i32, _u32, _pu64]),
+    "dse_consec_merge": (_i32, [_pu64, _pu64, _pu64]),
+    "dse_debug_consec_host": (_i32, [_pu64, _u64, _u64, _u32, _pu64]),
     "dse_debug_sums_host": (_i32, [_pu64, _u64, _u64, _u32, _u32, _pu64, _u32, _u32, _u32, _pu64]),
     "dse_debug_sums_recip": (_i32, [_pu64, _u64, _pu64]),
     "dse_debug_gaps_host": (_i32, [_pu64, _u64, _u64, _pu64]),

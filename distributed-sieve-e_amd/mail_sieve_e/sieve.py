@@ -246,6 +246,65 @@ def gaps_host(mask: np.ndarray, g_start: int, nbits: int) -> Gaps:
     return Gaps(out)
 
 
+class Consec:
+    """One dse_consec (include/dse.h "residue pairs of consecutive primes"): for the
+    modulus q the pairs of consecutive primes of the odd candidates [g_start, g_start
+    + nbits) by the classes of the lower and the upper prime. ``words`` is the struct
+    as its uint64 words."""
+
+    def __init__(self, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.shape != (_dse.CONSEC_WORDS,):
+            raise ValueError("a dse_consec is %d uint64 words" % _dse.CONSEC_WORDS)
+        self.words = w
+
+    @staticmethod
+    def _opt(v):
+        return None if v == _dse.CONSEC_NONE else v
+
+    g_start = property(lambda s: int(s.words[0]))
+    nbits = property(lambda s: int(s.words[1]))
+    q = property(lambda s: int(s.words[2]))
+    primes = property(lambda s: int(s.words[3]))
+    pairs = property(lambda s: int(s.words[4]))
+    first_g = property(lambda s: Consec._opt(int(s.words[5])))
+    last_g = property(lambda s: Consec._opt(int(s.words[6])))
+
+    @property
+    def counts(self) -> np.ndarray:
+        """uint64[64, 64]: the struct's counts[a * 64 + b]."""
+        return self.words[7:].reshape(_dse.CONSEC_MAX_MODULUS, _dse.CONSEC_MAX_MODULUS)
+
+    @property
+    def matrix(self) -> np.ndarray:
+        """uint64[q, q]: matrix[a, b] = pairs of consecutive primes p < p' with p = a
+        and p' = b (mod q)."""
+        return self.counts[:self.q, :self.q]
+
+    def merge(self, other: "Consec") -> "Consec":
+        """The matrix of this range followed by the adjacent ``other`` (dse_consec_merge)."""
+        out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
+        check(lib().dse_consec_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_consec_merge")
+        return Consec(out)
+
+    def __eq__(self, other):
+        return isinstance(other, Consec) and np.array_equal(self.words, other.words)
+
+    def __repr__(self):
+        return (f"Consec(g_start={self.g_start}, nbits={self.nbits}, q={self.q}, primes={self.primes}, "
+                f"pairs={self.pairs})")
+
+
+def consec_host(mask: np.ndarray, g_start: int, nbits: int, q: int) -> Consec:
+    """Test-only: the consec kernels' per-word bodies run on the host over a host mask
+    (include/dse.h dse_debug_consec_host)."""
+    out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
+    m = np.ascontiguousarray(mask, dtype=np.uint64)
+    check(lib().dse_debug_consec_host(u64p(m) if len(m) else None, g_start, nbits, q, u64p(out)),
+          "dse_debug_consec_host")
+    return Consec(out)
+
+
 class Sums:
     """One dse_sums (include/dse.h "power and reciprocal sums"): the matches of a
     pattern in the odd candidates [g_start, g_start + nbits), the sum of their values
@@ -736,6 +795,40 @@ class Context:
             return self.gaps_range(min((a - 3) // 2, 1 << 62), 0)
         b = hi if hi & 1 else hi - 1
         return self.gaps_range((a - 3) // 2, (b - a) // 2 + 1)
+
+    # -- residue pairs of consecutive primes ------------------------------------------
+    def consec_dev_async(self, g_start: int, nbits: int, mask_ptr: int, q: int, out_ptr: int, stream_ptr: int = 0):
+        """The pairs of consecutive primes of the device mask by their classes mod q as
+        one dse_consec (_dse.CONSEC_WORDS uint64 words) in device memory at out_ptr
+        (include/dse.h dse_consec_dev_async)."""
+        check(lib().dse_consec_dev_async(self.ptr, g_start, nbits, mask_ptr or None, q, out_ptr or None,
+                                         stream_ptr or None),
+              "dse_consec_dev_async")
+
+    def consec_range(self, g_start: int, nbits: int, q: int) -> Consec:
+        """gen-table + sieve-e of an odd-index range and the pairs of its consecutive
+        primes by their classes mod q, computed on the device: only the dse_consec
+        reaches the host."""
+        out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
+        check(lib().dse_consec_range(self.ptr, g_start, nbits, q, u64p(out)), "dse_consec_range")
+        return Consec(out)
+
+    def resident_consec(self, my_num: Optional[int] = None, q: int = 10) -> Consec:
+        """The matrix of a chunk the last sieve_all left on its device, or (my_num=None)
+        of all its chunks: the per-chunk results merged in order."""
+        out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
+        check(lib().dse_consec_resident(self.ptr, 0 if my_num is None else my_num, q, u64p(out)),
+              "dse_consec_resident")
+        return Consec(out)
+
+    def consec_window(self, lo: int, hi: int, q: int) -> Consec:
+        """The matrix of the odd values in [max(lo, 3), hi] (primes_window's convention);
+        an empty window gives the empty result."""
+        a = max(lo, 3) | 1
+        if hi < a:
+            return self.consec_range(min((a - 3) // 2, 1 << 62), 0, q)
+        b = hi if hi & 1 else hi - 1
+        return self.consec_range((a - 3) // 2, (b - a) // 2 + 1, q)
 
     # -- power and reciprocal sums ----------------------------------------------------
     def sums_dev_async(self, g_start: int, nbits: int, mask_ptr: int, require: int, forbid: int, above_ptr: int,

@@ -774,6 +774,66 @@ int32_t dse_sums_resident(dse_ctx *ctx, int32_t my_num, uint32_t require, uint32
  * merge is associative, with empty pieces on either side. */
 int32_t dse_sums_merge(const dse_sums *a, const dse_sums *b, dse_sums *out);
 
+/* ---- residue pairs of consecutive primes -------------------------------------- */
+
+/* The joint distribution of the classes mod q of consecutive primes of a device-resident mask, the
+ * q x q matrix N(a, b) = #{consecutive primes p < p' of the range : p = a, p' = b (mod q)} of Lemke
+ * Oliver and Soundararajan's "Unexpected biases in the distribution of consecutive primes" (2016),
+ * computed on the GPU in one read of the mask; only the dse_consec crosses to the host. Candidates,
+ * entries, values and g are dse_stats': candidate g is the value 3 + 2g, an entry is a set bit. The
+ * modulus is 3 <= q <= DSE_CONSEC_MAX_MODULUS, as dse_race's.
+ *
+ * A pair is two consecutive entries that both lie in the range (dse_gaps' rule for a gap).
+ * counts[a * 64 + b] = number of pairs whose lower value is = a and whose upper value is = b (mod q).
+ * Slots with a >= q or b >= q are 0, and so are the rows and columns of the residues that hold no
+ * odd candidate (q even, r even). A prime that divides q sits in its own class like any other: for
+ * q = 3 from g = 0 the pair (3, 5) is counts[0 * 64 + 2] = 1. The prime 2 is in no mask and the pair
+ * (2, 3) is never seen. pairs = primes - 1 (0 with fewer than two primes) = the sum of counts[]; the
+ * row sums of counts[] are dse_race's counts[] less the last entry, the column sums less the first.
+ *
+ * Every member is a uint64_t and there is no padding: bindings may treat a dse_consec as an array of
+ * DSE_CONSEC_WORDS uint64 words. */
+#define DSE_CONSEC_MAX_MODULUS 64
+#define DSE_CONSEC_NONE UINT64_MAX
+#define DSE_CONSEC_WORDS (7 + DSE_CONSEC_MAX_MODULUS * DSE_CONSEC_MAX_MODULUS)
+typedef struct dse_consec {
+  uint64_t g_start, nbits;   /* the range the numbers are of */
+  uint64_t q;
+  uint64_t primes;           /* set bits */
+  uint64_t pairs;            /* primes - 1, or 0 with fewer than two primes; == sum of counts[] */
+  uint64_t first_g, last_g;  /* first / last entry, DSE_CONSEC_NONE if none (dse_gaps' members) */
+  uint64_t counts[DSE_CONSEC_MAX_MODULUS * DSE_CONSEC_MAX_MODULUS]; /* counts[a * 64 + b] */
+} dse_consec;
+
+/* Async on stream, on a caller-owned device mask. out_dev: sizeof(dse_consec) bytes of device
+ * memory, 8-byte aligned; every member is written and nothing outside it is touched. Bits past nbits
+ * in the last word are ignored; nbits = 0 writes the empty result. DSE_EINVAL for a null ctx or
+ * out_dev, a null mask with nbits > 0, a misaligned out_dev or mask_dev, or q outside 3..64.
+ * DSE_ERANGE for a range beyond 2^62 or more than 2^44 candidates in one call. */
+int32_t dse_consec_dev_async(dse_ctx *ctx, uint64_t g_start, uint64_t nbits,
+                             const uint64_t *mask_dev, uint32_t q, dse_consec *out_dev,
+                             void *stream);
+
+/* gen-table + sieve-e + the matrix of an odd-index range, on the first device; host result. The
+ * range rules of dse_sieve_odd_range apply. */
+int32_t dse_consec_range(dse_ctx *ctx, uint64_t g_start, uint64_t nbits, uint32_t q,
+                         dse_consec *out);
+
+/* The matrix of chunk my_num left resident by the last dse_sieve_all; my_num = 0: of all P chunks,
+ * that is of [3, 3 + 2 P cs) (dse_stats_resident's convention). For all chunks, every chunk's
+ * launches are enqueued on its own device's stream before any is waited for, and the P results are
+ * merged on the host in chunk order: the merge rebuilds a seam's pair from the two sides' last and
+ * first entry, so no chunk sees its neighbour. DSE_EINVAL if the chunk is not resident. */
+int32_t dse_consec_resident(dse_ctx *ctx, int32_t my_num, uint32_t q, dse_consec *out);
+
+/* The matrix of the union of two adjacent ranges, by host arithmetic only; out may alias a or b.
+ * Needs a->g_start + a->nbits == b->g_start and a->q == b->q in 3..64 (else DSE_EINVAL; out is not
+ * touched); a union that ends above 2^62 gives DSE_ERANGE. counts and primes add; first_g / last_g
+ * come from whichever side has them. With an entry on both sides the seam's pair
+ * ((3 + 2 a->last_g) mod q, (3 + 2 b->first_g) mod q) is counted once; pairs is recomputed. The
+ * merge is associative, with empty and prime-less pieces on either side. */
+int32_t dse_consec_merge(const dse_consec *a, const dse_consec *b, dse_consec *out);
+
 /* ---- Test-only ---------------------------------------------------------- */
 
 /* Set a test-only option of this context (the production library reads no
@@ -831,6 +891,18 @@ int32_t dse_sums_merge(const dse_sums *a, const dse_sums *b, dse_sums *out);
  *   "sums_grid" = k in 1..1024: the dse_sums_* launches use at most k
  *   workgroups, so one workgroup walks several tiles and the closing launch
  *   adds several slabs on tiny inputs; 0 = default (one resident round).
+ *   "consec_grid" = k in 1..1024: the dse_consec_* launches use at most k
+ *   workgroups, so one workgroup walks several tiles and the closing launch
+ *   sums several slabs and counts their seams' pairs on tiny inputs; 0 =
+ *   default (one resident round).
+ *   "consec_flush_tiles" = k in 1..262143: a workgroup of the dse_consec_*
+ *   main kernel empties its 32-bit counters into its slab's 64-bit bins every
+ *   k tiles, so tiny inputs run the flush; 0 = default (262143 tiles: a bin
+ *   grows by at most 64 pairs per word and tile).
+ *   "consec_body" = 1: the in-word pairs are counted by the bit-parallel body
+ *   whenever it is built for the period (T <= 6); 2: by the per-entry body for
+ *   every period; 0 = default (the measured threshold). The results are the
+ *   same; the bench tool's A/B.
  * DSE_EINVAL for an unknown name or a value out of range. */
 int32_t dse_debug_set_option(dse_ctx *ctx, const char *name, int64_t value);
 
@@ -953,6 +1025,14 @@ int32_t dse_debug_race_host(const uint64_t *mask, uint64_t g_start, uint64_t nbi
  * same bits. Test-only; DSE_EINVAL / DSE_ERANGE as dse_gaps_dev_async for the
  * pointers and the range. */
 int32_t dse_debug_gaps_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, dse_gaps *out);
+
+/* The dse_consec_* kernels' own per-word bodies, run on the host in a plain loop over
+ * the tiles and words of a host mask (no device call), the in-word pairs by the body
+ * the launch would take for q: the same result as dse_consec_dev_async on the same
+ * bits. Test-only; DSE_EINVAL / DSE_ERANGE as dse_consec_dev_async for the pointers,
+ * q and the range. */
+int32_t dse_debug_consec_host(const uint64_t *mask, uint64_t g_start, uint64_t nbits, uint32_t q,
+                              dse_consec *out);
 
 /* The dse_sums_* kernels' own per-word and per-entry bodies, run on the host in a plain loop over
  * the words of a host mask and a host `above` (no device call), the device's division routine

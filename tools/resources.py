@@ -25,7 +25,8 @@ def main(extra):
            ("dse_wheel_half.hip", make_var("WHEEL_FLAGS")), ("dse_wheel_plain.hip", make_var("PLAIN_FLAGS")),
            ("dse_base.hip", []), ("dse_finish.hip", []), ("dse_primes.hip", []), ("dse_stats.hip", []),
            ("dse_query.hip", []), ("dse_goldbach.hip", make_var("GOLDBACH_FLAGS")),
-           ("dse_race.hip", []), ("dse_tuples.hip", []), ("dse_gaps.hip", []), ("dse_sums.hip", [])]
+           ("dse_race.hip", []), ("dse_tuples.hip", []), ("dse_gaps.hip", []), ("dse_sums.hip", []),
+           ("dse_consec.hip", [])]
     for tu, fl in tus:
         if not os.path.exists(os.path.join(CSRC, tu)):
             continue
