@@ -42,8 +42,9 @@ constexpr uint32_t kGbWaves = kGbThreads / 64;
 // workgroups per compute unit of the one resident round the grid is: 4 with the 16 register counters of
 // the production build (93 VGPRs; kGbMaxGrid holds 4 x 256 CUs), 3 for A/B builds with more (make resources)
 constexpr uint32_t kGbGridPerCu = kGbRegRanks > 16 ? 3 : 4;
-// the register counters are 32 bits wide and grow by at most 64 per tile: summed into LDS this often
-constexpr uint32_t kGbFlushTiles = 1u << 20;
+// the register counters are 32 bits wide and grow by at most 64 per tile; they are summed per wave in 32 bits
+// and then into LDS this often, so that a wave's sum cannot wrap (kSlabFlushTiles, dse_slab.h)
+constexpr uint32_t kGbFlushTiles = kSlabFlushTiles;
 static_assert(kGbLineWords <= 2 * kGbThreads, "a thread stages at most two words of a line");
 static_assert(kGbRegRanks <= kGbPrimes && kGbTable.h(kGbRegRanks - 1) <= 64 * kGbLowWords,
               "the unrolled windows stay in the line");

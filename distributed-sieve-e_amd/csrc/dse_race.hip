@@ -38,8 +38,9 @@ namespace {
 constexpr uint32_t kRcThreads = kMaskTileWords;  // one mask word per thread
 constexpr uint32_t kRcWaves = kRcThreads / 64;
 constexpr uint32_t kRcGridPerCu = 4;  // workgroups per compute unit of the one resident round the grid is
-// the count kernel's register counters are 32 bits wide and grow by at most 64 per tile: summed into LDS after this many
-constexpr uint32_t kRcFlushTiles = 1u << 20;
+// the count kernel's register counters are 32 bits wide and grow by at most 64 per tile; they are summed per wave in
+// 32 bits and then into LDS after this many tiles, so that a wave's sum cannot wrap (kSlabFlushTiles, dse_slab.h)
+constexpr uint32_t kRcFlushTiles = kSlabFlushTiles;
 
 // a workgroup's slab, in uint64 words: the scalars are the main kernel's, the bins the count kernel's
 constexpr uint32_t kSlAAhead = 0, kSlBAhead = 1, kSlFirstA = 2, kSlFirstB = 3, kSlMaxD = 4, kSlMaxG = 5, kSlMinD = 6,

@@ -23,6 +23,14 @@ namespace dse {
 constexpr uint32_t kSlabCloseThreads = 1024;  // the closing kernel: one thread per slab
 constexpr uint32_t kSlabCloseBins = 64;       // and 64 bins per workgroup
 
+// Tiles after which a main kernel with one mask word per thread (dse_stats.hip, dse_race.hip,
+// dse_goldbach.hip) empties its 32-bit register counters into LDS. A counter grows by at most 64 per
+// tile (the bits of the thread's word), and the flush sums it over a wave in 32 bits first (wave_sum),
+// so it is the wave's sum that must fit: 64 lanes x 64 x tiles <= 2^32 - 1, tiles <= 1,048,575. (2^20
+// tiles is one too many: an all-ones run's wave sum is 2^32 exactly and wraps to 0.)
+constexpr uint32_t kSlabFlushTiles = 0xFFFFFFFFu / (64u * 64u);
+static_assert(64ull * 64ull * kSlabFlushTiles <= 0xFFFFFFFFull, "a wave's sum of the counters fits 32 bits");
+
 // Workgroups of the main launch: every workgroup walks one fixed run of tiles, so the grid is one
 // resident round of per_cu workgroups per compute unit (what the main kernel's registers admit,
 // make resources), at most max_grid, 0 exactly for an empty range. grid_cap > 0: the tests' cap.

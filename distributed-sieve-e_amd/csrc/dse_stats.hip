@@ -39,8 +39,9 @@ namespace {
 constexpr uint32_t kStThreads = kMaskTileWords;  // one mask word per thread
 constexpr uint32_t kStWaves = kStThreads / 64;
 constexpr uint32_t kStDepth = 3;  // tiles loaded together, one group ahead of the one worked on
-// per-thread counters are 32 bits wide and grow by at most 64 per tile: summed into LDS this often
-constexpr uint32_t kStFlushTiles = 1u << 20;
+// per-thread counters are 32 bits wide and grow by at most 64 per tile; they are summed per wave in 32
+// bits and then into LDS this often, so that a wave's sum cannot wrap (kSlabFlushTiles, dse_slab.h)
+constexpr uint32_t kStFlushTiles = kSlabFlushTiles;
 
 // a workgroup's slab, in uint64 words
 constexpr uint32_t kSlPrimes = 0, kSlFirst = 1, kSlLast1 = 2, kSlMaxD = 3, kSlMaxI = 4, kSlOverflow = 5, kSlBins = 6,
