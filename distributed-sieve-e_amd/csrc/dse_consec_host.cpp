@@ -32,18 +32,11 @@ hipError_t consec_launch(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const u
 
 extern "C" int32_t dse_consec_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
                                         uint32_t q, dse_consec* out_dev, void* stream) {
-  if (!ctx || !out_dev) return fail(DSE_EINVAL, "null ctx or out");
-  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
-  if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(mask_dev) & 7u) return fail(DSE_EINVAL, "mask_dev is not 8-byte aligned");
   int32_t rc;
+  if ((rc = check_dev_args(ctx, nbits, mask_dev, out_dev, "out", true))) return rc;
   if ((rc = consec_check(q))) return rc;
   if ((rc = check_mask_range("consec", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  HIP_TRY(hipSetDevice(d.device));
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t grid = consec_grid(nbits, d.num_cus, ctx->consec_grid);
-  return scratch_launch(d.consec_scratch, consec_scratch_bytes(grid), s, "consec launch", [&](void* slabs) {
+  return unit_dev_async<kUnitConsec>(ctx, nbits, stream, [&](void* slabs, uint32_t grid, hipStream_t s) {
     return consec_launch(ctx, g_start, nbits, mask_dev, q, reinterpret_cast<uint64_t*>(out_dev), slabs, grid, s);
   });
 }
@@ -53,23 +46,12 @@ extern "C" int32_t dse_consec_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbi
   int32_t rc;
   if ((rc = consec_check(q))) return rc;
   if ((rc = check_mask_range("consec", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
-  HIP_TRY(hipSetDevice(d.device));
-  const uint32_t grid = consec_grid(nbits, d.num_cus, ctx->consec_grid);
-  uint64_t* res;
-  if ((rc = result_acquire(d, d.consec_scratch, consec_scratch_bytes(grid), 1, sizeof(dse_consec), 0, &res, nullptr)))
-    return rc;
-  const hipError_t e = consec_launch(ctx, g_start, nbits, d.scratch_mask.as<uint64_t>(), q, res,
-                                     d.consec_scratch.buf.ptr, grid, d.stream);
-  if (e != hipSuccess) {
-    (void)release_scratch(&d.consec_scratch, d.stream);
-    return fail(DSE_EHIP, std::string("consec launch failed: ") + hipGetErrorString(e));
-  }
-  dse_consec tmp;
-  if ((rc = result_collect(d, d.consec_scratch, "consec", res, sizeof tmp, &tmp))) return rc;
-  *out = tmp;
-  return DSE_OK;
+  return unit_range<kUnitConsec>(
+      ctx, g_start, nbits, nbits,
+      [&](const uint64_t* mask, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        return consec_launch(ctx, g_start, nbits, mask, q, res, slabs, grid, s);
+      },
+      out);
 }
 
 extern "C" int32_t dse_consec_resident(dse_ctx* ctx, int32_t my_num, uint32_t q, dse_consec* out) {
@@ -79,34 +61,21 @@ extern "C" int32_t dse_consec_resident(dse_ctx* ctx, int32_t my_num, uint32_t q,
   if ((rc = resident_span(ctx, my_num, "consec", &k0, &k1))) return rc;
   const ResidentSet& r = ctx->resident;
   const uint64_t cs = (uint64_t)r.cs;
-  return resident_reduce<dse_consec>(
-      ctx, k0, k1, &DevState::consec_scratch, "consec",
-      [&](DevState& d, const std::vector<int32_t>& chunks, uint64_t** res, bool* acquired) -> int32_t {
-        const uint32_t n = (uint32_t)chunks.size(), grid = consec_grid(cs, d.num_cus, ctx->consec_grid);
-        StreamScratch& s = d.consec_scratch;
-        int32_t ra = result_acquire(d, s, consec_scratch_bytes(grid), n, sizeof(dse_consec), 0, res, nullptr);
-        if (ra) return ra;
-        *acquired = true;
-        hipError_t e = hipSuccess;
-        for (uint32_t j = 0; j < n && e == hipSuccess; ++j) {
-          const size_t c = (size_t)chunks[j] - 1;
-          e = consec_launch(ctx, (uint64_t)c * cs, cs, r.masks[c].as<uint64_t>(), q,
-                            *res + (uint64_t)j * DSE_CONSEC_WORDS, s.buf.ptr, grid, d.stream);
-        }
-        if (e != hipSuccess) return fail(DSE_EHIP, std::string("consec launch failed: ") + hipGetErrorString(e));
-        return DSE_OK;
+  return unit_resident<kUnitConsec>(
+      ctx, k0, k1, 0,
+      [&](DevState&, int32_t k, uint64_t*, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        const uint64_t* const mask = r.masks[(size_t)k - 1].as<uint64_t>();
+        return consec_launch(ctx, (uint64_t)(k - 1) * cs, cs, mask, q, res, slabs, grid, s);
       },
       dse_consec_merge, out);
 }
 
 extern "C" int32_t dse_consec_merge(const dse_consec* a, const dse_consec* b, dse_consec* out) {
   if (!a || !b || !out) return fail(DSE_EINVAL, "null consec result");
-  if (a->g_start + a->nbits != b->g_start || a->g_start > b->g_start)
-    return fail(DSE_EINVAL, "the ranges are not adjacent");
+  if (int32_t rc = check_merge_adjacent(a->g_start, a->nbits, b->g_start)) return rc;
   if (a->q != b->q || a->q < 3 || a->q > DSE_CONSEC_MAX_MODULUS)
     return fail(DSE_EINVAL, "the results are of different moduli");
-  if (b->g_start > (1ull << 62) || b->nbits > (1ull << 62) - b->g_start)
-    return fail(DSE_ERANGE, "merged range beyond 2^62");
+  if (int32_t rc = check_merge_end(b->g_start, b->nbits)) return rc;
   dse_consec r = *a;  // out may alias a or b
   r.nbits = a->nbits + b->nbits;
   r.primes = a->primes + b->primes;

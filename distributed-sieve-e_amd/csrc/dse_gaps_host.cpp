@@ -27,41 +27,23 @@ void gaps_recount(dse_gaps* r) {
 
 extern "C" int32_t dse_gaps_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
                                       dse_gaps* out_dev, void* stream) {
-  if (!ctx || !out_dev) return fail(DSE_EINVAL, "null ctx or out");
-  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
-  if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
   int32_t rc;
+  if ((rc = check_dev_args(ctx, nbits, mask_dev, out_dev, "out", false))) return rc;
   if ((rc = check_mask_range("gaps", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  HIP_TRY(hipSetDevice(d.device));
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t grid = gaps_grid(nbits, d.num_cus, ctx->gaps_grid);
-  return scratch_launch(d.gaps_scratch, gaps_scratch_bytes(grid), s, "gaps launch", [&](void* slabs) {
+  return unit_dev_async<kUnitGaps>(ctx, nbits, stream, [&](void* slabs, uint32_t grid, hipStream_t s) {
     return launch_gaps(g_start, nbits, mask_dev, reinterpret_cast<uint64_t*>(out_dev), slabs, grid, s);
   });
 }
 
 extern "C" int32_t dse_gaps_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, dse_gaps* out) {
   if (!ctx || !out) return fail(DSE_EINVAL, "null ctx or out");
-  int32_t rc;
-  if ((rc = check_mask_range("gaps", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
-  HIP_TRY(hipSetDevice(d.device));
-  const uint32_t grid = gaps_grid(nbits, d.num_cus, ctx->gaps_grid);
-  uint64_t* res;
-  if ((rc = result_acquire(d, d.gaps_scratch, gaps_scratch_bytes(grid), 1, sizeof(dse_gaps), 0, &res, nullptr)))
-    return rc;
-  const hipError_t e =
-      launch_gaps(g_start, nbits, d.scratch_mask.as<uint64_t>(), res, d.gaps_scratch.buf.ptr, grid, d.stream);
-  if (e != hipSuccess) {
-    (void)release_scratch(&d.gaps_scratch, d.stream);
-    return fail(DSE_EHIP, std::string("gaps launch failed: ") + hipGetErrorString(e));
-  }
-  dse_gaps tmp;
-  if ((rc = result_collect(d, d.gaps_scratch, "gaps", res, sizeof tmp, &tmp))) return rc;
-  *out = tmp;
-  return DSE_OK;
+  if (int32_t rc = check_mask_range("gaps", g_start, nbits)) return rc;
+  return unit_range<kUnitGaps>(
+      ctx, g_start, nbits, nbits,
+      [&](const uint64_t* mask, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        return launch_gaps(g_start, nbits, mask, res, slabs, grid, s);
+      },
+      out);
 }
 
 extern "C" int32_t dse_gaps_resident(dse_ctx* ctx, int32_t my_num, dse_gaps* out) {
@@ -70,32 +52,18 @@ extern "C" int32_t dse_gaps_resident(dse_ctx* ctx, int32_t my_num, dse_gaps* out
   if ((rc = resident_span(ctx, my_num, "gaps", &k0, &k1))) return rc;
   const ResidentSet& r = ctx->resident;
   const uint64_t cs = (uint64_t)r.cs;
-  return resident_reduce<dse_gaps>(
-      ctx, k0, k1, &DevState::gaps_scratch, "gaps",
-      [&](DevState& d, const std::vector<int32_t>& chunks, uint64_t** res, bool* acquired) -> int32_t {
-        const uint32_t n = (uint32_t)chunks.size(), grid = gaps_grid(cs, d.num_cus, ctx->gaps_grid);
-        StreamScratch& s = d.gaps_scratch;
-        int32_t ra = result_acquire(d, s, gaps_scratch_bytes(grid), n, sizeof(dse_gaps), 0, res, nullptr);
-        if (ra) return ra;
-        *acquired = true;
-        hipError_t e = hipSuccess;
-        for (uint32_t j = 0; j < n && e == hipSuccess; ++j) {
-          const size_t c = (size_t)chunks[j] - 1;
-          e = launch_gaps((uint64_t)c * cs, cs, r.masks[c].as<uint64_t>(), *res + (uint64_t)j * DSE_GAPS_WORDS,
-                          s.buf.ptr, grid, d.stream);
-        }
-        if (e != hipSuccess) return fail(DSE_EHIP, std::string("gaps launch failed: ") + hipGetErrorString(e));
-        return DSE_OK;
+  return unit_resident<kUnitGaps>(
+      ctx, k0, k1, 0,
+      [&](DevState&, int32_t k, uint64_t*, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        return launch_gaps((uint64_t)(k - 1) * cs, cs, r.masks[(size_t)k - 1].as<uint64_t>(), res, slabs, grid, s);
       },
       dse_gaps_merge, out);
 }
 
 extern "C" int32_t dse_gaps_merge(const dse_gaps* a, const dse_gaps* b, dse_gaps* out) {
   if (!a || !b || !out) return fail(DSE_EINVAL, "null gaps");
-  if (a->g_start + a->nbits != b->g_start || a->g_start > b->g_start)
-    return fail(DSE_EINVAL, "the ranges are not adjacent");
-  if (b->g_start > (1ull << 62) || b->nbits > (1ull << 62) - b->g_start)
-    return fail(DSE_ERANGE, "merged range beyond 2^62");
+  if (int32_t rc = check_merge_adjacent(a->g_start, a->nbits, b->g_start)) return rc;
+  if (int32_t rc = check_merge_end(b->g_start, b->nbits)) return rc;
 
   // the seam's gap: s places at a's last prime, above every position of a and below every one of b
   const bool seam = a->last_g != DSE_GAPS_NONE && b->first_g != DSE_GAPS_NONE;

@@ -57,20 +57,13 @@ extern "C" uint64_t dse_goldbach_reach(uint32_t nprimes) {
 extern "C" int32_t dse_goldbach_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
                                           const uint64_t* below_dev, uint32_t below_shift, uint64_t below_bits,
                                           uint32_t nprimes, dse_goldbach* out_dev, void* stream) {
-  if (!ctx || !out_dev) return fail(DSE_EINVAL, "null ctx or out");
-  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
-  if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(mask_dev) & 7u) return fail(DSE_EINVAL, "mask_dev is not 8-byte aligned");
   int32_t rc;
+  if ((rc = check_dev_args(ctx, nbits, mask_dev, out_dev, "out", true))) return rc;
   uint32_t n;
   if ((rc = gb_nprimes(nprimes, &n))) return rc;
   if ((rc = gb_check_below(below_dev, below_shift, below_bits, g_start))) return rc;
   if ((rc = check_mask_range("goldbach", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  HIP_TRY(hipSetDevice(d.device));
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t grid = goldbach_grid(nbits, d.num_cus, ctx->goldbach_grid);
-  return scratch_launch(d.goldbach_scratch, goldbach_scratch_bytes(grid), s, "goldbach launch", [&](void* slabs) {
+  return unit_dev_async<kUnitGoldbach>(ctx, nbits, stream, [&](void* slabs, uint32_t grid, hipStream_t s) {
     return launch_goldbach(g_start, nbits, mask_dev, 0, below_dev, below_shift, below_bits, n,
                            reinterpret_cast<uint64_t*>(out_dev), slabs, grid, s);
   });
@@ -87,26 +80,13 @@ extern "C" int32_t dse_goldbach_range(dse_ctx* ctx, uint64_t g_start, uint64_t n
   const uint64_t reach = kGbTable.h(n - 1);
   const uint64_t ext = nbits ? std::min(g_start, reach) : 0;
   if ((rc = check_mask_range("goldbach", g_start - ext, nbits + ext))) return rc;
-  DevState& d = ctx->devs[0];
-  if (nbits && (rc = sieve_range_host(ctx, d, g_start - ext, nbits + ext, nullptr, nullptr, true))) return rc;
-  HIP_TRY(hipSetDevice(d.device));
   // one scratch mask: `below` is its first ext bits, the range's own mask starts ext bits in
-  const uint64_t* const m = d.scratch_mask.as<uint64_t>();
-  const uint32_t grid = goldbach_grid(nbits, d.num_cus, ctx->goldbach_grid);
-  uint64_t* res;
-  if ((rc = result_acquire(d, d.goldbach_scratch, goldbach_scratch_bytes(grid), 1, sizeof(dse_goldbach), 0, &res,
-                           nullptr)))
-    return rc;
-  const hipError_t e = launch_goldbach(g_start, nbits, m + (ext >> 6), (uint32_t)(ext & 63), m, 0, ext, n, res,
-                                       d.goldbach_scratch.buf.ptr, grid, d.stream);
-  if (e != hipSuccess) {
-    (void)release_scratch(&d.goldbach_scratch, d.stream);
-    return fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
-  }
-  dse_goldbach tmp;
-  if ((rc = result_collect(d, d.goldbach_scratch, "goldbach", res, sizeof tmp, &tmp))) return rc;
-  *out = tmp;
-  return DSE_OK;
+  return unit_range<kUnitGoldbach>(
+      ctx, g_start - ext, nbits + ext, nbits,
+      [&](const uint64_t* m, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        return launch_goldbach(g_start, nbits, m + (ext >> 6), (uint32_t)(ext & 63), m, 0, ext, n, res, slabs, grid, s);
+      },
+      out);
 }
 
 extern "C" int32_t dse_goldbach_resident(dse_ctx* ctx, int32_t my_num, uint32_t nprimes, dse_goldbach* out) {
@@ -126,56 +106,41 @@ extern "C" int32_t dse_goldbach_resident(dse_ctx* ctx, int32_t my_num, uint32_t 
   const uint64_t off = cs - (k1 > 1 ? reach : 0);                          // the tail's first bit in a chunk's mask
   const uint32_t tail_shift = (uint32_t)(off & 63);
   const uint64_t tail_words = k1 > 1 ? below_words(tail_shift, reach) : 0;  // through the mask's last word
-
   const size_t nd = ctx->devs.size();
-  auto enqueue = [&](DevState& d, const std::vector<int32_t>& chunks, uint64_t** res, bool* acquired) -> int32_t {
-    const uint32_t cnt = (uint32_t)chunks.size();
-    const uint32_t grid = goldbach_grid(cs, d.num_cus, ctx->goldbach_grid);
-    uint64_t* copies = nullptr;
-    if (int32_t ra = result_acquire(d, d.goldbach_scratch, goldbach_scratch_bytes(grid), cnt, sizeof(dse_goldbach),
-                                    (nd > 1 ? cnt : 0) * tail_words * 8, res, &copies))
-      return ra;
-    *acquired = true;
-    hipError_t e = hipSuccess;
-    for (uint32_t j = 0; j < cnt && e == hipSuccess; ++j) {
-      const int32_t k = chunks[j];
-      const uint64_t* below = nullptr;
-      uint64_t below_bits = 0;
-      if (k > 1 && reach) {
-        const DevState& sd = ctx->devs[(size_t)(k - 2) % nd];
-        const uint64_t* const tail = r.masks[k - 2].as<uint64_t>() + (off >> 6);
-        below_bits = reach;
-        if (&sd == &d) {
-          below = tail;  // the neighbour's mask is this device's: a pointer into it
-        } else {
-          // the neighbour's whole words into this device's scratch, on this device's stream: the
-          // launch behind it is ordered by the stream, the scratch's next user by its event
-          uint64_t* const dst = copies + (uint64_t)j * tail_words;
-          e = sd.device == d.device
-                  ? hipMemcpyAsync(dst, tail, tail_words * 8, hipMemcpyDeviceToDevice, d.stream)
-                  : hipMemcpyPeerAsync(dst, d.device, tail, sd.device, tail_words * 8, d.stream);
-          below = dst;
+  return unit_resident<kUnitGoldbach>(
+      ctx, k0, k1, nd > 1 ? tail_words : 0,  // behind the results: a neighbour's tail per chunk
+      [&](DevState& d, int32_t k, uint64_t* copy, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        const uint64_t* below = nullptr;
+        uint64_t below_bits = 0;
+        hipError_t e = hipSuccess;
+        if (k > 1 && reach) {
+          const DevState& sd = ctx->devs[(size_t)(k - 2) % nd];
+          const uint64_t* const tail = r.masks[k - 2].as<uint64_t>() + (off >> 6);
+          below_bits = reach;
+          if (&sd == &d) {
+            below = tail;  // the neighbour's mask is this device's: a pointer into it
+          } else {
+            // the neighbour's whole words into this device's scratch, on this device's stream: the
+            // launch behind it is ordered by the stream, the scratch's next user by its event
+            e = sd.device == d.device ? hipMemcpyAsync(copy, tail, tail_words * 8, hipMemcpyDeviceToDevice, s)
+                                      : hipMemcpyPeerAsync(copy, d.device, tail, sd.device, tail_words * 8, s);
+            below = copy;
+          }
         }
-      }
-      if (e == hipSuccess)
-        e = launch_goldbach((uint64_t)(k - 1) * cs, cs, r.masks[k - 1].as<uint64_t>(), 0, below, tail_shift, below_bits,
-                            n, *res + (uint64_t)j * DSE_GOLDBACH_WORDS, d.goldbach_scratch.buf.ptr, grid, d.stream);
-    }
-    if (e != hipSuccess) return fail(DSE_EHIP, std::string("goldbach launch failed: ") + hipGetErrorString(e));
-    return DSE_OK;
-  };
-  return resident_reduce<dse_goldbach>(ctx, k0, k1, &DevState::goldbach_scratch, "goldbach", enqueue,
-                                       dse_goldbach_merge, out);
+        if (e == hipSuccess)
+          e = launch_goldbach((uint64_t)(k - 1) * cs, cs, r.masks[k - 1].as<uint64_t>(), 0, below, tail_shift, below_bits,
+                              n, res, slabs, grid, s);
+        return e;
+      },
+      dse_goldbach_merge, out);
 }
 
 extern "C" int32_t dse_goldbach_merge(const dse_goldbach* a, const dse_goldbach* b, dse_goldbach* out) {
   if (!a || !b || !out) return fail(DSE_EINVAL, "null goldbach result");
-  if (a->g_start + a->nbits != b->g_start || a->g_start > b->g_start)
-    return fail(DSE_EINVAL, "the ranges are not adjacent");
+  if (int32_t rc = check_merge_adjacent(a->g_start, a->nbits, b->g_start)) return rc;
   if (a->nprimes != b->nprimes || a->nprimes < 1 || a->nprimes > DSE_GOLDBACH_PRIMES)
     return fail(DSE_EINVAL, "the results are of different nprimes");
-  if (b->g_start > (1ull << 62) || b->nbits > (1ull << 62) - b->g_start)
-    return fail(DSE_ERANGE, "merged range beyond 2^62");
+  if (int32_t rc = check_merge_end(b->g_start, b->nbits)) return rc;
   dse_goldbach r;  // out may alias a or b
   r.g_start = a->g_start;
   r.nbits = a->nbits + b->nbits;

@@ -146,6 +146,32 @@ int32_t result_collect(DevState& d, StreamScratch& s, const char* what, const ui
   return DSE_OK;
 }
 
+int32_t launch_rc(const SlabUnitDesc& u, hipError_t e) {
+  if (e != hipSuccess) return fail(DSE_EHIP, std::string(u.name) + " launch failed: " + hipGetErrorString(e));
+  return DSE_OK;
+}
+
+int32_t check_dev_args(const dse_ctx* ctx, uint64_t nbits, const void* mask_dev, const void* out_dev, const char* out,
+                       bool mask_aligned) {
+  if (!ctx || !out_dev) return fail(DSE_EINVAL, std::string("null ctx or ") + out);
+  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
+  if (reinterpret_cast<uintptr_t>(out_dev) & 7u)
+    return fail(DSE_EINVAL, std::string(out) + "_dev is not 8-byte aligned");
+  if (mask_aligned && (reinterpret_cast<uintptr_t>(mask_dev) & 7u))
+    return fail(DSE_EINVAL, "mask_dev is not 8-byte aligned");
+  return DSE_OK;
+}
+
+int32_t check_merge_adjacent(uint64_t a_g, uint64_t a_nbits, uint64_t b_g) {
+  if (a_g + a_nbits != b_g || a_g > b_g) return fail(DSE_EINVAL, "the ranges are not adjacent");
+  return DSE_OK;
+}
+
+int32_t check_merge_end(uint64_t b_g, uint64_t b_nbits) {
+  if (b_g > (1ull << 62) || b_nbits > (1ull << 62) - b_g) return fail(DSE_ERANGE, "merged range beyond 2^62");
+  return DSE_OK;
+}
+
 int32_t resident_fanout(dse_ctx* ctx, int32_t k0, int32_t k1, const FanEnqueue& enqueue, const FanCollect& collect) {
   const size_t nd = ctx->devs.size();
   std::vector<std::vector<int32_t>> chunks(nd);
@@ -528,13 +554,7 @@ const struct {
      [](dse_ctx* c, int64_t v) { c->finish_slab_words = (uint64_t)v; }},
     {"primes_slab_entries", 0, kI64Max, "must be >= 0",
      [](dse_ctx* c, int64_t v) { c->primes_slab_entries = (uint64_t)v; }},
-    {"stats_grid", 0, (int64_t)kStatsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->stats_grid = (uint32_t)v; }},
     {"query_grid", 0, (int64_t)kQueryMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->query_grid = (uint32_t)v; }},
-    {"goldbach_grid", 0, (int64_t)kGbMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->goldbach_grid = (uint32_t)v; }},
-    {"race_grid", 0, (int64_t)kRaceMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->race_grid = (uint32_t)v; }},
-    {"gaps_grid", 0, (int64_t)kGapsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->gaps_grid = (uint32_t)v; }},
-    {"sums_grid", 0, (int64_t)kSumsMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->sums_grid = (uint32_t)v; }},
-    {"consec_grid", 0, (int64_t)kConsecMaxGrid, "out of range", [](dse_ctx* c, int64_t v) { c->consec_grid = (uint32_t)v; }},
     {"consec_flush_tiles", 0, (int64_t)kConsecFlushTiles, "out of range",
      [](dse_ctx* c, int64_t v) { c->consec_flush_tiles = (uint32_t)v; }},
     {"consec_body", 0, 2, "must be 0, 1 or 2", [](dse_ctx* c, int64_t v) { c->consec_body = (uint32_t)v; }},
@@ -647,13 +667,8 @@ void dse_destroy(dse_ctx* ctx) {
     free_slab_pipe(d.pipe);
     (void)free_scratch(&d.finish_sums);
     (void)free_scratch(&d.primes_sums);
-    (void)free_scratch(&d.stats_scratch);
     (void)free_scratch(&d.query_scratch);
-    (void)free_scratch(&d.goldbach_scratch);
-    (void)free_scratch(&d.race_scratch);
-    (void)free_scratch(&d.gaps_scratch);
-    (void)free_scratch(&d.sums_scratch);
-    (void)free_scratch(&d.consec_scratch);
+    for (StreamScratch& s : d.unit_scratch) (void)free_scratch(&s);
     if (d.xev) (void)hipEventDestroy(d.xev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }
@@ -868,6 +883,12 @@ int32_t dse_debug_set_option(dse_ctx* ctx, const char* name, int64_t value) {
     if (n == o.name) {
       if (value < o.min || value > o.max) return fail(DSE_EINVAL, n + " " + o.bad);
       o.set(ctx, value);
+      return DSE_OK;
+    }
+  for (uint32_t u = 0; u < kNumSlabUnits; ++u)  // "<unit>_grid"
+    if (n == std::string(kSlabUnits[u].name) + "_grid") {
+      if (value < 0 || value > (int64_t)kSlabUnits[u].max_grid) return fail(DSE_EINVAL, n + " out of range");
+      ctx->grid_cap[u] = (uint32_t)value;
       return DSE_OK;
     }
   if (n == "bucket_lo_log2") {

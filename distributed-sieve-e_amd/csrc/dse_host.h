@@ -1,10 +1,20 @@
-// dse_host.h -- shared by the units of the C-ABI host layer (dse_host.cpp:
-// contexts, tables, collectives, sieve entry points; dse_finish_host.cpp: the
-// primes{k}.txt writers; dse_primes_host.cpp: primes as numbers;
-// dse_stats_host.cpp: statistics of a mask; dse_query_host.cpp: rank and
-// select; dse_goldbach_host.cpp: minimal Goldbach partitions; dse_race_host.cpp: residue classes
-// and races; dse_tuples_host.cpp: constellations as numbers; dse_gaps_host.cpp: where the gaps are; dse_sums_host.cpp: power and reciprocal sums; dse_consec_host.cpp: residue pairs of consecutive primes): contexts, device state, the slab
-// pipe, and the result pass over resident chunks. Not installed; include/dse.h is the ABI.
+// dse_host.h -- shared by the units of the C-ABI host layer. Not installed;
+// include/dse.h is the ABI.
+//   dse_host.cpp           contexts, tables, collectives, sieve entry points
+//   dse_finish_host.cpp    the primes{k}.txt writers
+//   dse_primes_host.cpp    primes as numbers
+//   dse_tuples_host.cpp    constellations as numbers
+//   dse_query_host.cpp     rank and select
+//   dse_stats_host.cpp     statistics of a mask
+//   dse_goldbach_host.cpp  minimal Goldbach partitions
+//   dse_race_host.cpp      residue classes and races
+//   dse_gaps_host.cpp      where the gaps are
+//   dse_sums_host.cpp      power and reciprocal sums
+//   dse_consec_host.cpp    residue pairs of consecutive primes
+// Here: contexts and device state, the slab pipe and the rank pipeline of the
+// units that bring values to the host, and for the last six, the slab units
+// (dse_slab.h: a mask becomes one small struct), their table and the three
+// drivers of their entry points.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -34,6 +44,27 @@ int32_t fail(int32_t code, const std::string& msg);
     if (r_ != ncclSuccess)                                                                     \
       return dse::fail(DSE_ENCCL, std::string(#expr " failed: ") + ncclGetErrorString(r_));    \
   } while (0)
+
+// The slab units: six passes that turn a mask into one small struct through the
+// slab reduction of dse_slab.h. One row each: the name of its messages and of
+// its test option "<name>_grid", its grid and scratch rules (dse_internal.h),
+// the largest grid and the uint64 words of its result.
+enum SlabUnit : uint32_t { kUnitStats, kUnitGoldbach, kUnitRace, kUnitGaps, kUnitSums, kUnitConsec, kNumSlabUnits };
+struct SlabUnitDesc {
+  const char* name;
+  uint32_t (*grid)(uint64_t nbits, int num_cus, uint32_t grid_cap);
+  uint64_t (*scratch_bytes)(uint32_t grid);
+  uint32_t max_grid;
+  uint32_t words;
+};
+inline constexpr SlabUnitDesc kSlabUnits[kNumSlabUnits] = {
+    {"stats", stats_grid, stats_scratch_bytes, kStatsMaxGrid, DSE_STATS_WORDS},
+    {"goldbach", goldbach_grid, goldbach_scratch_bytes, kGbMaxGrid, DSE_GOLDBACH_WORDS},
+    {"race", race_grid, race_scratch_bytes, kRaceMaxGrid, DSE_RACE_WORDS},
+    {"gaps", gaps_grid, gaps_scratch_bytes, kGapsMaxGrid, DSE_GAPS_WORDS},
+    {"sums", sums_grid, sums_scratch_bytes, kSumsMaxGrid, DSE_SUMS_WORDS},
+    {"consec", consec_grid, consec_scratch_bytes, kConsecMaxGrid, DSE_CONSEC_WORDS},
+};
 
 // The two-slot slab pipe of the blocking entry points that bring a device
 // result to the host in slabs (finish text, prime values): slab i + 1 is
@@ -65,16 +96,19 @@ struct DevState {
   Buf counts;                // device scratch (unsigned long long)
   Buf scratch_mask;          // for dse_sieve_chunk
   Scratch scratch;           // bucketed-pass scratch (high-offset ranges)
-  SlabPipe pipe;             // slabs to the host: finish text, prime values, constellation values
-  StreamScratch finish_sums; // device finish (dse_finish.hip): tile-sum scratch of the three launches
-  StreamScratch primes_sums; // primes and constellations as numbers (dse_primes.hip, dse_tuples.hip): tile-sum scratch of the three launches; dse_tuples_resident's totals and head words
-  StreamScratch stats_scratch; // statistics (dse_stats.hip): the workgroups' slabs, and results on their way to the host
-  StreamScratch query_scratch; // rank and select (dse_query.hip): queries and answers on their way, dse_query_range's index
-  StreamScratch goldbach_scratch; // Goldbach partitions (dse_goldbach.hip): the workgroups' slabs, results on their way to the host, a neighbour chunk's tail
-  StreamScratch race_scratch; // residue classes and races (dse_race.hip): the workgroups' slabs, results on their way to the host
-  StreamScratch gaps_scratch; // where the gaps are (dse_gaps.hip): the workgroups' slabs, results on their way to the host
-  StreamScratch sums_scratch; // power and reciprocal sums (dse_sums.hip): the workgroups' slabs, results on their way to the host, a neighbour chunk's head words
-  StreamScratch consec_scratch; // residue pairs of consecutive primes (dse_consec.hip): the workgroups' slabs, results on their way to the host
+  SlabPipe pipe;             // slabs to the host: finish text, prime and constellation values
+  // tile-sum scratch of the three launches of the device finish (dse_finish.hip)
+  StreamScratch finish_sums;
+  // the same of primes and constellations as numbers (dse_primes.hip,
+  // dse_tuples.hip), and dse_tuples_resident's totals and head words
+  StreamScratch primes_sums;
+  // rank and select (dse_query.hip): queries and answers on their way,
+  // dse_query_range's index
+  StreamScratch query_scratch;
+  // one per slab unit, so that the units stay independent of each other on
+  // different streams: the workgroups' slabs, results on their way to the host
+  // and what a chunk sees of its neighbour (Goldbach: a tail, sums: a head word)
+  StreamScratch unit_scratch[kNumSlabUnits];
   hipEvent_t xev = nullptr;  // logical devices: this device's side of a collective
 };
 
@@ -106,17 +140,13 @@ struct dse_ctx {
   std::vector<ncclComm_t> comms;
   dse::ResidentSet resident;
   dse::SieveOpts opts;  // test-only knobs (dse_debug_set_option)
-  uint64_t finish_slab_words = 0;  // test-only: > 0 caps a finish slab at that many mask words
-  uint64_t primes_slab_entries = 0;  // test-only: > 0 caps a slab of dse_primes_range / _resident at that many values
-  uint32_t stats_grid = 0;  // test-only: > 0 caps the workgroups of a statistics launch
-  uint32_t query_grid = 0;  // test-only: > 0 caps the workgroups of a query launch
-  uint32_t goldbach_grid = 0;  // test-only: > 0 caps the workgroups of a Goldbach launch
-  uint32_t race_grid = 0;  // test-only: > 0 caps the workgroups of a race launch
-  uint32_t gaps_grid = 0;  // test-only: > 0 caps the workgroups of a gaps launch
-  uint32_t sums_grid = 0;  // test-only: > 0 caps the workgroups of a sums launch
-  uint32_t consec_grid = 0;  // test-only: > 0 caps the workgroups of a consec launch
-  uint32_t consec_flush_tiles = 0;  // test-only: > 0: the tiles after which a consec workgroup empties its 32-bit counters
-  uint32_t consec_body = 0;  // test-only: 1 / 2 force the bit-parallel / per-entry body of the consec main kernel
+  // test-only knobs of the units (dse_debug_set_option); 0 leaves each alone
+  uint64_t finish_slab_words = 0;    // caps a finish slab at that many mask words
+  uint64_t primes_slab_entries = 0;  // caps a slab of dse_primes_range / _resident at that many values
+  uint32_t query_grid = 0;           // caps the workgroups of a query launch
+  uint32_t grid_cap[dse::kNumSlabUnits] = {};  // "<unit>_grid": caps the workgroups of that slab unit's launch
+  uint32_t consec_flush_tiles = 0;   // the tiles after which a consec workgroup empties its 32-bit counters
+  uint32_t consec_body = 0;          // 1 / 2 force the bit-parallel / per-entry body of the consec main kernel
   int64_t query_index_builds = 0;  // rank indices built for resident chunks (dse_debug_get_stat)
   // dse_debug_init_logical: every DevState on device 0, the collectives
   // replaced by copies (xfer_table / allreduce_counts); on device 0:
@@ -178,32 +208,116 @@ using FanEnqueue = std::function<int32_t(size_t, DevState&, const std::vector<in
 using FanCollect = std::function<int32_t(size_t, DevState&, const std::vector<int32_t>&)>;
 int32_t resident_fanout(dse_ctx* ctx, int32_t k0, int32_t k1, const FanEnqueue& enqueue, const FanCollect& collect);
 
-// One result R per chunk k0 .. k1, folded into *out in chunk order by the unit's merge. enqueue(
-// DevState&, its chunks, &res, &acquired) result_acquires d.*scratch with one R per chunk at *res.
-template <typename R, typename Enqueue>
-int32_t resident_reduce(dse_ctx* ctx, int32_t k0, int32_t k1, StreamScratch DevState::*scratch, const char* what,
-                        Enqueue&& enqueue, int32_t (*merge)(const R*, const R*, R*), R* out) {
-  std::vector<R> parts((size_t)(k1 - k0 + 1)), got;
+// The drivers of the slab units' entry points (U: the unit, R: its struct of include/dse.h). Each
+// entry point checks its own arguments first, in its own order; a launch callable hands the
+// addresses and the grid it is given to the unit's launch_* and returns its hipError_t, which a
+// driver reports as "<unit> launch failed: ..." (launch_rc), or an int32_t it has reported itself.
+int32_t launch_rc(const SlabUnitDesc& u, hipError_t e);
+inline int32_t launch_rc(const SlabUnitDesc&, int32_t rc) { return rc; }
+// The pointer checks at the head of a *_dev_async entry point: "null ctx or <out>", "null mask",
+// "<out>_dev is not 8-byte aligned" and, for the units that refuse one, a misaligned mask_dev.
+int32_t check_dev_args(const dse_ctx* ctx, uint64_t nbits, const void* mask_dev, const void* out_dev, const char* out,
+                       bool mask_aligned);
+// The range checks every dse_*_merge shares: "the ranges are not adjacent" (DSE_EINVAL) opens it,
+// "merged range beyond 2^62" (DSE_ERANGE) follows the unit's own checks of the pair.
+int32_t check_merge_adjacent(uint64_t a_g, uint64_t a_nbits, uint64_t b_g);
+int32_t check_merge_end(uint64_t b_g, uint64_t b_nbits);
+
+// *_dev_async: launch(slabs, grid, stream) on device 0 around the unit's scratch (scratch_launch).
+template <SlabUnit U, typename Launch>
+int32_t unit_dev_async(dse_ctx* ctx, uint64_t nbits, void* stream, Launch&& launch) {
+  constexpr const SlabUnitDesc& u = kSlabUnits[U];
+  DevState& d = ctx->devs[0];
+  HIP_TRY(hipSetDevice(d.device));
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t grid = u.grid(nbits, d.num_cus, ctx->grid_cap[U]);
+  return scratch_launch(d.unit_scratch[U], u.scratch_bytes(grid), s, (std::string(u.name) + " launch").c_str(),
+                        [&](void* slabs) { return launch(slabs, grid, s); });
+}
+
+// *_range: the candidates [sieve_g, sieve_g + sieve_bits) are sieved into device 0's scratch mask
+// (the unit's nbits of them and what it sees beside them; nothing for an empty range), then
+// launch(that mask, result, slabs, grid, stream) and the result to *out. The scratch is released
+// after a failed launch too; *out is written only on success.
+template <SlabUnit U, typename R, typename Launch>
+int32_t unit_range(dse_ctx* ctx, uint64_t sieve_g, uint64_t sieve_bits, uint64_t nbits, Launch&& launch, R* out) {
+  constexpr const SlabUnitDesc& u = kSlabUnits[U];
+  static_assert(sizeof(R) == 8 * u.words, "R is the unit's struct");
+  DevState& d = ctx->devs[0];
+  StreamScratch& s = d.unit_scratch[U];
+  int32_t rc;
+  if (nbits && (rc = sieve_range_host(ctx, d, sieve_g, sieve_bits, nullptr, nullptr, true))) return rc;
+  HIP_TRY(hipSetDevice(d.device));
+  const uint32_t grid = u.grid(nbits, d.num_cus, ctx->grid_cap[U]);
+  uint64_t* res;
+  if ((rc = result_acquire(d, s, u.scratch_bytes(grid), 1, sizeof(R), 0, &res, nullptr))) return rc;
+  if ((rc = launch_rc(u, launch(d.scratch_mask.as<uint64_t>(), res, s.buf.ptr, grid, d.stream)))) {
+    (void)release_scratch(&s, d.stream);
+    return rc;
+  }
+  R tmp;
+  if ((rc = result_collect(d, s, u.name, res, sizeof tmp, &tmp))) return rc;
+  *out = tmp;
+  return DSE_OK;
+}
+
+// *_resident, the parts: one R per resident chunk k0 .. k1 into (*parts)[k - k0]. On every device
+// that holds some (resident_fanout), behind the slabs one R per chunk and extra_words uint64 per
+// chunk of the unit's own, then chunk(d, k, extra, result, slabs, grid, stream) for each of its
+// chunks k in order, until one fails: it may copy a neighbour's words into `extra` on the stream
+// and launches on chunk k's mask. Every device's launches are enqueued before any result is waited for.
+template <SlabUnit U, typename R, typename Chunk>
+int32_t unit_resident_parts(dse_ctx* ctx, int32_t k0, int32_t k1, uint64_t extra_words, Chunk&& chunk,
+                            std::vector<R>* parts) {
+  constexpr const SlabUnitDesc& u = kSlabUnits[U];
+  static_assert(sizeof(R) == 8 * u.words, "R is the unit's struct");
+  const uint64_t cs = (uint64_t)ctx->resident.cs;
+  parts->clear();
+  parts->resize((size_t)(k1 - k0 + 1));
   std::vector<uint64_t*> res(ctx->devs.size(), nullptr);
-  int32_t rc = resident_fanout(
+  std::vector<R> got;
+  return resident_fanout(
       ctx, k0, k1,
-      [&](size_t i, DevState& d, const std::vector<int32_t>& chunks, bool* acquired) {
-        return enqueue(d, chunks, &res[i], acquired);
+      [&](size_t i, DevState& d, const std::vector<int32_t>& chunks, bool* acquired) -> int32_t {
+        const uint32_t n = (uint32_t)chunks.size(), grid = u.grid(cs, d.num_cus, ctx->grid_cap[U]);
+        StreamScratch& s = d.unit_scratch[U];
+        uint64_t* extra;
+        int32_t rc = result_acquire(d, s, u.scratch_bytes(grid), n, sizeof(R), n * extra_words * 8, &res[i], &extra);
+        if (rc) return rc;
+        *acquired = true;
+        for (uint32_t j = 0; j < n && !rc; ++j)
+          rc = launch_rc(u, chunk(d, chunks[j], extra + j * extra_words, res[i] + (uint64_t)j * u.words, s.buf.ptr,
+                                  grid, d.stream));
+        return rc;
       },
       [&](size_t i, DevState& d, const std::vector<int32_t>& chunks) {
         got.resize(chunks.size());
-        const int32_t r = result_collect(d, d.*scratch, what, res[i], chunks.size() * sizeof(R), got.data());
-        if (!r)
-          for (size_t j = 0; j < got.size(); ++j) parts[(size_t)(chunks[j] - k0)] = got[j];
-        return r;
+        const int32_t rc = result_collect(d, d.unit_scratch[U], u.name, res[i], chunks.size() * sizeof(R), got.data());
+        if (!rc)
+          for (size_t j = 0; j < got.size(); ++j) (*parts)[(size_t)(chunks[j] - k0)] = got[j];
+        return rc;
       });
-  if (rc) return rc;
+}
+
+// The parts (at least one), folded into *out in chunk order by the unit's merge.
+template <typename R>
+int32_t merge_parts(const std::vector<R>& parts, int32_t (*merge)(const R*, const R*, R*), R* out) {
   R acc = parts[0];
   for (size_t j = 1; j < parts.size(); ++j)
-    if ((rc = merge(&acc, &parts[j], &acc))) return rc;
+    if (int32_t rc = merge(&acc, &parts[j], &acc)) return rc;
   *out = acc;
   return DSE_OK;
 }
+
+// *_resident: unit_resident_parts, then merge_parts.
+template <SlabUnit U, typename R, typename Chunk>
+int32_t unit_resident(dse_ctx* ctx, int32_t k0, int32_t k1, uint64_t extra_words, Chunk&& chunk,
+                      int32_t (*merge)(const R*, const R*, R*), R* out) {
+  std::vector<R> parts;
+  if (int32_t rc = unit_resident_parts<U>(ctx, k0, k1, extra_words, chunk, &parts)) return rc;
+  return merge_parts(parts, merge, out);
+}
+
 // The pattern and `above` rules of the units that match a pattern against the visible candidates
 // (dse_tuples_host.cpp, dse_sums_host.cpp): DSE_EINVAL as dse_tuples_dev_async documents them.
 int32_t tuples_check_pattern(uint32_t require, uint32_t forbid);

@@ -38,59 +38,18 @@ void race_empty(dse_race* r, uint64_t g_start, uint64_t nbits, uint32_t q, uint3
   r->first_a_ahead = r->first_b_ahead = r->max_g = r->min_g = DSE_RACE_NONE;
 }
 
-// One dse_race per resident chunk k0 .. k1 into parts[k - k0]: chunk k with the classes (a, b) from
-// d_starts[k - k0]. Every device's launches are enqueued before any result is waited for.
-int32_t race_chunks(dse_ctx* ctx, int32_t k0, int32_t k1, uint32_t q, uint32_t a, uint32_t b,
-                    const std::vector<int64_t>& d_starts, std::vector<dse_race>* parts) {
-  const ResidentSet& r = ctx->resident;
-  const uint64_t cs = (uint64_t)r.cs;
-  parts->assign((size_t)(k1 - k0 + 1), dse_race());
-  std::vector<uint64_t*> res(ctx->devs.size(), nullptr);
-  std::vector<dse_race> got;
-  return resident_fanout(
-      ctx, k0, k1,
-      [&](size_t i, DevState& d, const std::vector<int32_t>& chunks, bool* acquired) -> int32_t {
-        const uint32_t n = (uint32_t)chunks.size(), grid = race_grid(cs, d.num_cus, ctx->race_grid);
-        StreamScratch& s = d.race_scratch;
-        if (int32_t ra = result_acquire(d, s, race_scratch_bytes(grid), n, sizeof(dse_race), 0, &res[i], nullptr))
-          return ra;
-        *acquired = true;
-        hipError_t e = hipSuccess;
-        for (uint32_t j = 0; j < n && e == hipSuccess; ++j) {
-          const size_t c = (size_t)chunks[j] - 1;
-          e = launch_race((uint64_t)c * cs, cs, r.masks[c].as<uint64_t>(), q, a, b, d_starts[c + 1 - (size_t)k0],
-                          res[i] + (uint64_t)j * DSE_RACE_WORDS, s.buf.ptr, grid, d.stream);
-        }
-        if (e != hipSuccess) return fail(DSE_EHIP, std::string("race launch failed: ") + hipGetErrorString(e));
-        return DSE_OK;
-      },
-      [&](size_t i, DevState& d, const std::vector<int32_t>& chunks) {
-        got.resize(chunks.size());
-        const int32_t rc = result_collect(d, d.race_scratch, "race", res[i], chunks.size() * sizeof(dse_race), got.data());
-        if (!rc)
-          for (size_t j = 0; j < got.size(); ++j) (*parts)[(size_t)(chunks[j] - k0)] = got[j];
-        return rc;
-      });
-}
-
 }  // namespace
 
 extern "C" int32_t dse_race_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
                                       uint32_t q, uint32_t a, uint32_t b, int64_t d_start, dse_race* out_dev,
                                       void* stream) {
-  if (!ctx || !out_dev) return fail(DSE_EINVAL, "null ctx or out");
-  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
-  if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(mask_dev) & 7u) return fail(DSE_EINVAL, "mask_dev is not 8-byte aligned");
   int32_t rc;
+  if ((rc = check_dev_args(ctx, nbits, mask_dev, out_dev, "out", true))) return rc;
   if ((rc = race_check(q, a, b, d_start))) return rc;
   if ((rc = check_mask_range("race", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  HIP_TRY(hipSetDevice(d.device));
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t grid = race_grid(nbits, d.num_cus, ctx->race_grid);
-  return scratch_launch(d.race_scratch, race_scratch_bytes(grid), s, "race launch", [&](void* slabs) {
-    return launch_race(g_start, nbits, mask_dev, q, a, b, d_start, reinterpret_cast<uint64_t*>(out_dev), slabs, grid, s);
+  return unit_dev_async<kUnitRace>(ctx, nbits, stream, [&](void* slabs, uint32_t grid, hipStream_t s) {
+    return launch_race(g_start, nbits, mask_dev, q, a, b, d_start, reinterpret_cast<uint64_t*>(out_dev), slabs, grid,
+                       s);
   });
 }
 
@@ -100,23 +59,12 @@ extern "C" int32_t dse_race_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits
   int32_t rc;
   if ((rc = race_check(q, a, b, d_start))) return rc;
   if ((rc = check_mask_range("race", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
-  HIP_TRY(hipSetDevice(d.device));
-  const uint32_t grid = race_grid(nbits, d.num_cus, ctx->race_grid);
-  uint64_t* res;
-  if ((rc = result_acquire(d, d.race_scratch, race_scratch_bytes(grid), 1, sizeof(dse_race), 0, &res, nullptr)))
-    return rc;
-  const hipError_t e = launch_race(g_start, nbits, d.scratch_mask.as<uint64_t>(), q, a, b, d_start, res,
-                                   d.race_scratch.buf.ptr, grid, d.stream);
-  if (e != hipSuccess) {
-    (void)release_scratch(&d.race_scratch, d.stream);
-    return fail(DSE_EHIP, std::string("race launch failed: ") + hipGetErrorString(e));
-  }
-  dse_race tmp;
-  if ((rc = result_collect(d, d.race_scratch, "race", res, sizeof tmp, &tmp))) return rc;
-  *out = tmp;
-  return DSE_OK;
+  return unit_range<kUnitRace>(
+      ctx, g_start, nbits, nbits,
+      [&](const uint64_t* mask, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        return launch_race(g_start, nbits, mask, q, a, b, d_start, res, slabs, grid, s);
+      },
+      out);
 }
 
 extern "C" int32_t dse_race_resident(dse_ctx* ctx, int32_t my_num, uint32_t q, uint32_t a, uint32_t b,
@@ -126,32 +74,38 @@ extern "C" int32_t dse_race_resident(dse_ctx* ctx, int32_t my_num, uint32_t q, u
   if ((rc = race_check(q, a, b, d_start))) return rc;
   int32_t k0, k1;
   if ((rc = resident_span(ctx, my_num, "race", &k0, &k1))) return rc;
+  const ResidentSet& r = ctx->resident;
+  const uint64_t cs = (uint64_t)r.cs;
   const size_t n = (size_t)(k1 - k0 + 1);
   std::vector<int64_t> d_starts(n, d_start);
   std::vector<dse_race> parts;
+  // one dse_race per chunk: chunk k with the classes (a, b2) from ds[k - k0]
+  auto pass = [&](uint32_t b2, const std::vector<int64_t>& ds) {
+    return unit_resident_parts<kUnitRace>(
+        ctx, k0, k1, 0,
+        [&](DevState&, int32_t k, uint64_t*, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+          return launch_race((uint64_t)(k - 1) * cs, cs, r.masks[(size_t)k - 1].as<uint64_t>(), q, a, b2,
+                             ds[(size_t)(k - k0)], res, slabs, grid, s);
+        },
+        &parts);
+  };
   if (n > 1 && a != b) {
     // chunk k + 1 starts from chunk k's d_end: the chunks' class counts first, on every device
-    if ((rc = race_chunks(ctx, k0, k1, q, a, a, std::vector<int64_t>(n, 0), &parts))) return rc;
+    if ((rc = pass(a, std::vector<int64_t>(n, 0)))) return rc;
     for (size_t j = 1; j < n; ++j)
       d_starts[j] = d_starts[j - 1] + (int64_t)parts[j - 1].counts[a] - (int64_t)parts[j - 1].counts[b];
   }
-  if ((rc = race_chunks(ctx, k0, k1, q, a, b, d_starts, &parts))) return rc;
-  dse_race acc = parts[0];
-  for (size_t j = 1; j < n; ++j)
-    if ((rc = dse_race_merge(&acc, &parts[j], &acc))) return rc;
-  *out = acc;
-  return DSE_OK;
+  if ((rc = pass(b, d_starts))) return rc;
+  return merge_parts(parts, dse_race_merge, out);
 }
 
 extern "C" int32_t dse_race_merge(const dse_race* a, const dse_race* b, dse_race* out) {
   if (!a || !b || !out) return fail(DSE_EINVAL, "null race result");
-  if (a->g_start + a->nbits != b->g_start || a->g_start > b->g_start)
-    return fail(DSE_EINVAL, "the ranges are not adjacent");
+  if (int32_t rc = check_merge_adjacent(a->g_start, a->nbits, b->g_start)) return rc;
   if (a->q != b->q || a->a != b->a || a->b != b->b || a->q < 3 || a->q > DSE_RACE_MAX_MODULUS)
     return fail(DSE_EINVAL, "the results are of different races");
   if (b->d_start != a->d_end) return fail(DSE_EINVAL, "the second range does not start from the first one's d_end");
-  if (b->g_start > (1ull << 62) || b->nbits > (1ull << 62) - b->g_start)
-    return fail(DSE_ERANGE, "merged range beyond 2^62");
+  if (int32_t rc = check_merge_end(b->g_start, b->nbits)) return rc;
   dse_race r = *a;  // out may alias a or b
   r.nbits = a->nbits + b->nbits;
   r.d_end = b->d_end;

@@ -35,17 +35,11 @@ inline bool seam_bit(const dse_stats& a, const dse_stats& b, uint32_t q) {
 extern "C" int32_t dse_stats_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t nbits, const uint64_t* mask_dev,
                                        const uint32_t* patterns, uint32_t npatterns, dse_stats* stats_dev,
                                        void* stream) {
-  if (!ctx || !stats_dev) return fail(DSE_EINVAL, "null ctx or stats");
-  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
-  if (reinterpret_cast<uintptr_t>(stats_dev) & 7u) return fail(DSE_EINVAL, "stats_dev is not 8-byte aligned");
   int32_t rc;
+  if ((rc = check_dev_args(ctx, nbits, mask_dev, stats_dev, "stats", false))) return rc;
   if ((rc = stats_check_patterns(patterns, npatterns))) return rc;
   if ((rc = check_mask_range("stats", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  HIP_TRY(hipSetDevice(d.device));
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t grid = stats_grid(nbits, d.num_cus, ctx->stats_grid);
-  return scratch_launch(d.stats_scratch, stats_scratch_bytes(grid), s, "stats launch", [&](void* slabs) {
+  return unit_dev_async<kUnitStats>(ctx, nbits, stream, [&](void* slabs, uint32_t grid, hipStream_t s) {
     return launch_stats(g_start, nbits, mask_dev, patterns, npatterns, reinterpret_cast<uint64_t*>(stats_dev), slabs,
                         grid, s);
   });
@@ -57,23 +51,12 @@ extern "C" int32_t dse_stats_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbit
   int32_t rc;
   if ((rc = stats_check_patterns(patterns, npatterns))) return rc;
   if ((rc = check_mask_range("stats", g_start, nbits))) return rc;
-  DevState& d = ctx->devs[0];
-  if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits, nullptr, nullptr, true))) return rc;
-  HIP_TRY(hipSetDevice(d.device));
-  const uint32_t grid = stats_grid(nbits, d.num_cus, ctx->stats_grid);
-  uint64_t* res;
-  if ((rc = result_acquire(d, d.stats_scratch, stats_scratch_bytes(grid), 1, sizeof(dse_stats), 0, &res, nullptr)))
-    return rc;
-  const hipError_t e = launch_stats(g_start, nbits, d.scratch_mask.as<uint64_t>(), patterns, npatterns, res,
-                                    d.stats_scratch.buf.ptr, grid, d.stream);
-  if (e != hipSuccess) {
-    (void)release_scratch(&d.stats_scratch, d.stream);
-    return fail(DSE_EHIP, std::string("stats launch failed: ") + hipGetErrorString(e));
-  }
-  dse_stats tmp;
-  if ((rc = result_collect(d, d.stats_scratch, "stats", res, sizeof tmp, &tmp))) return rc;
-  *out = tmp;
-  return DSE_OK;
+  return unit_range<kUnitStats>(
+      ctx, g_start, nbits, nbits,
+      [&](const uint64_t* mask, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        return launch_stats(g_start, nbits, mask, patterns, npatterns, res, slabs, grid, s);
+      },
+      out);
 }
 
 extern "C" int32_t dse_stats_resident(dse_ctx* ctx, int32_t my_num, const uint32_t* patterns, uint32_t npatterns,
@@ -85,35 +68,22 @@ extern "C" int32_t dse_stats_resident(dse_ctx* ctx, int32_t my_num, const uint32
   if ((rc = resident_span(ctx, my_num, "stats", &k0, &k1))) return rc;
   const ResidentSet& r = ctx->resident;
   const uint64_t cs = (uint64_t)r.cs;
-  return resident_reduce<dse_stats>(
-      ctx, k0, k1, &DevState::stats_scratch, "stats",
-      [&](DevState& d, const std::vector<int32_t>& chunks, uint64_t** res, bool* acquired) -> int32_t {
-        const uint32_t n = (uint32_t)chunks.size(), grid = stats_grid(cs, d.num_cus, ctx->stats_grid);
-        StreamScratch& s = d.stats_scratch;
-        int32_t ra = result_acquire(d, s, stats_scratch_bytes(grid), n, sizeof(dse_stats), 0, res, nullptr);
-        if (ra) return ra;
-        *acquired = true;
-        hipError_t e = hipSuccess;
-        for (uint32_t j = 0; j < n && e == hipSuccess; ++j) {
-          const size_t c = (size_t)chunks[j] - 1;
-          e = launch_stats((uint64_t)c * cs, cs, r.masks[c].as<uint64_t>(), patterns, npatterns,
-                           *res + (uint64_t)j * DSE_STATS_WORDS, s.buf.ptr, grid, d.stream);
-        }
-        if (e != hipSuccess) return fail(DSE_EHIP, std::string("stats launch failed: ") + hipGetErrorString(e));
-        return DSE_OK;
+  return unit_resident<kUnitStats>(
+      ctx, k0, k1, 0,
+      [&](DevState&, int32_t k, uint64_t*, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        return launch_stats((uint64_t)(k - 1) * cs, cs, r.masks[(size_t)k - 1].as<uint64_t>(), patterns, npatterns, res,
+                            slabs, grid, s);
       },
       dse_stats_merge, out);
 }
 
 extern "C" int32_t dse_stats_merge(const dse_stats* a, const dse_stats* b, dse_stats* out) {
   if (!a || !b || !out) return fail(DSE_EINVAL, "null stats");
-  if (a->g_start + a->nbits != b->g_start || a->g_start > b->g_start)
-    return fail(DSE_EINVAL, "the ranges are not adjacent");
+  if (int32_t rc = check_merge_adjacent(a->g_start, a->nbits, b->g_start)) return rc;
   if (a->npatterns != b->npatterns || a->npatterns > DSE_STATS_MAX_PATTERNS ||
       std::memcmp(a->pattern, b->pattern, sizeof a->pattern))
     return fail(DSE_EINVAL, "the pattern lists differ");
-  if (b->g_start > (1ull << 62) || b->nbits > (1ull << 62) - b->g_start)
-    return fail(DSE_ERANGE, "merged range beyond 2^62");
+  if (int32_t rc = check_merge_end(b->g_start, b->nbits)) return rc;
 
   dse_stats r;
   std::memset(&r, 0, sizeof r);

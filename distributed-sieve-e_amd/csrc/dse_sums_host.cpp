@@ -30,20 +30,14 @@ extern "C" int32_t dse_sums_dev_async(dse_ctx* ctx, uint64_t g_start, uint64_t n
                                       uint32_t require, uint32_t forbid, const uint64_t* above_dev,
                                       uint32_t above_shift, uint32_t above_bits, uint32_t flags, dse_sums* out_dev,
                                       void* stream) {
-  if (!ctx || !out_dev) return fail(DSE_EINVAL, "null ctx or out");
-  if (nbits && !mask_dev) return fail(DSE_EINVAL, "null mask");
-  if (reinterpret_cast<uintptr_t>(out_dev) & 7u) return fail(DSE_EINVAL, "out_dev is not 8-byte aligned");
   int32_t rc;
+  if ((rc = check_dev_args(ctx, nbits, mask_dev, out_dev, "out", false))) return rc;
   if ((rc = sums_check(require, forbid, flags))) return rc;
   if ((rc = tuples_check_above(above_dev, above_shift, above_bits))) return rc;
   if ((rc = check_mask_range("sums", g_start, nbits))) return rc;
   if ((rc = check_odd_range(g_start, nbits + above_bits))) return rc;
-  DevState& d = ctx->devs[0];
-  HIP_TRY(hipSetDevice(d.device));
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t grid = sums_grid(nbits, d.num_cus, ctx->sums_grid);
   const TuplePattern p{require, forbid, above_dev, above_shift, above_bits};
-  return scratch_launch(d.sums_scratch, sums_scratch_bytes(grid), s, "sums launch", [&](void* slabs) {
+  return unit_dev_async<kUnitSums>(ctx, nbits, stream, [&](void* slabs, uint32_t grid, hipStream_t s) {
     return launch_sums(g_start, nbits, mask_dev, p, flags, reinterpret_cast<uint64_t*>(out_dev), slabs, grid, s);
   });
 }
@@ -58,24 +52,13 @@ extern "C" int32_t dse_sums_range(dse_ctx* ctx, uint64_t g_start, uint64_t nbits
   // fewer where the sieve's last candidate (the odd index 2^61 - 2) ends them
   const uint64_t top = (1ull << 61) - 1, end = g_start + nbits;
   const uint64_t ext = nbits && end < top ? std::min<uint64_t>(kTuplesMaxAbove, top - end) : 0;
-  DevState& d = ctx->devs[0];
-  if (nbits && (rc = sieve_range_host(ctx, d, g_start, nbits + ext, nullptr, nullptr, true))) return rc;
-  HIP_TRY(hipSetDevice(d.device));
-  const uint64_t* const m = d.scratch_mask.as<uint64_t>();
-  const TuplePattern p{require, forbid, ext ? m + (nbits >> 6) : nullptr, (uint32_t)(nbits & 63), (uint32_t)ext};
-  const uint32_t grid = sums_grid(nbits, d.num_cus, ctx->sums_grid);
-  uint64_t* res;
-  if ((rc = result_acquire(d, d.sums_scratch, sums_scratch_bytes(grid), 1, sizeof(dse_sums), 0, &res, nullptr)))
-    return rc;
-  const hipError_t e = launch_sums(g_start, nbits, m, p, flags, res, d.sums_scratch.buf.ptr, grid, d.stream);
-  if (e != hipSuccess) {
-    (void)release_scratch(&d.sums_scratch, d.stream);
-    return fail(DSE_EHIP, std::string("sums launch failed: ") + hipGetErrorString(e));
-  }
-  dse_sums tmp;
-  if ((rc = result_collect(d, d.sums_scratch, "sums", res, sizeof tmp, &tmp))) return rc;
-  *out = tmp;
-  return DSE_OK;
+  return unit_range<kUnitSums>(
+      ctx, g_start, nbits + ext, nbits,
+      [&](const uint64_t* m, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) {
+        const TuplePattern p{require, forbid, ext ? m + (nbits >> 6) : nullptr, (uint32_t)(nbits & 63), (uint32_t)ext};
+        return launch_sums(g_start, nbits, m, p, flags, res, slabs, grid, s);
+      },
+      out);
 }
 
 extern "C" int32_t dse_sums_resident(dse_ctx* ctx, int32_t my_num, uint32_t require, uint32_t forbid, uint32_t flags,
@@ -87,32 +70,22 @@ extern "C" int32_t dse_sums_resident(dse_ctx* ctx, int32_t my_num, uint32_t requ
   const ResidentSet& r = ctx->resident;
   const uint64_t cs = (uint64_t)r.cs;
   if (cs && (rc = resident_above_check(ctx, k0))) return rc;
-  return resident_reduce<dse_sums>(
-      ctx, k0, k1, &DevState::sums_scratch, "sums",
-      [&](DevState& d, const std::vector<int32_t>& chunks, uint64_t** res, bool* acquired) -> int32_t {
-        const uint32_t n = (uint32_t)chunks.size(), grid = sums_grid(cs, d.num_cus, ctx->sums_grid);
-        StreamScratch& s = d.sums_scratch;
-        uint64_t* heads;  // behind the results: a neighbour's head word per chunk
-        int32_t ra = result_acquire(d, s, sums_scratch_bytes(grid), n, sizeof(dse_sums), n * 8ull, res, &heads);
-        if (ra) return ra;
-        *acquired = true;
-        for (uint32_t j = 0; j < n; ++j) {
-          const int32_t k = chunks[j];
-          TuplePattern p{require, forbid, nullptr, 0, 0};
-          if (cs && k < r.P && (ra = resident_above(ctx, d, k, heads + j, &p))) return ra;
-          const hipError_t e = launch_sums((uint64_t)(k - 1) * cs, cs, r.masks[(size_t)k - 1].as<uint64_t>(), p, flags,
-                                           *res + (uint64_t)j * DSE_SUMS_WORDS, s.buf.ptr, grid, d.stream);
-          if (e != hipSuccess) return fail(DSE_EHIP, std::string("sums launch failed: ") + hipGetErrorString(e));
-        }
-        return DSE_OK;
+  return unit_resident<kUnitSums>(
+      ctx, k0, k1, 1,  // behind the results: a neighbour's head word per chunk
+      [&](DevState& d, int32_t k, uint64_t* head, uint64_t* res, void* slabs, uint32_t grid, hipStream_t s) -> int32_t {
+        TuplePattern p{require, forbid, nullptr, 0, 0};
+        if (cs && k < r.P)
+          if (int32_t ra = resident_above(ctx, d, k, head, &p)) return ra;
+        const uint64_t* const mask = r.masks[(size_t)k - 1].as<uint64_t>();
+        return launch_rc(kSlabUnits[kUnitSums],
+                         launch_sums((uint64_t)(k - 1) * cs, cs, mask, p, flags, res, slabs, grid, s));
       },
       dse_sums_merge, out);
 }
 
 extern "C" int32_t dse_sums_merge(const dse_sums* a, const dse_sums* b, dse_sums* out) {
   if (!a || !b || !out) return fail(DSE_EINVAL, "null sums");
-  if (a->g_start + a->nbits != b->g_start || a->g_start > b->g_start)
-    return fail(DSE_EINVAL, "the ranges are not adjacent");
+  if (int32_t rc = check_merge_adjacent(a->g_start, a->nbits, b->g_start)) return rc;
   if (a->require != b->require || a->forbid != b->forbid || a->flags != b->flags)
     return fail(DSE_EINVAL, "the sums are of different patterns or flags");
   if (int32_t rc = sums_check(a->require, a->forbid, a->flags)) return rc;
@@ -120,8 +93,7 @@ extern "C" int32_t dse_sums_merge(const dse_sums* a, const dse_sums* b, dse_sums
   const uint64_t span = tuples_span((uint32_t)a->require, (uint32_t)a->forbid);
   if (a->above_bits < std::min<uint64_t>(span - 1, b->nbits + b->above_bits))
     return fail(DSE_EINVAL, "the lower range saw too few candidates above it");
-  if (b->g_start > (1ull << 62) || b->nbits > (1ull << 62) - b->g_start)
-    return fail(DSE_ERANGE, "merged range beyond 2^62");
+  if (int32_t rc = check_merge_end(b->g_start, b->nbits)) return rc;
 
   dse_sums r = *a;
   r.nbits = a->nbits + b->nbits;

@@ -92,31 +92,65 @@ def _patterns(patterns):
     return ((ctypes.c_uint32 * len(pats))(*pats) if pats else None), len(pats)
 
 
-class Stats:
+class _Result:
+    """What the results of the six slab units share: ``words``, the struct of
+    include/dse.h as its WORDS uint64 words, with NONE for "no such candidate", and
+    dse_<UNIT>_merge for the results of adjacent ranges."""
+
+    UNIT: str
+    WORDS: int
+    NONE: int
+
+    def __init__(self, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.shape != (self.WORDS,):
+            raise ValueError("a dse_%s is %d uint64 words" % (self.UNIT, self.WORDS))
+        self.words = w
+
+    @classmethod
+    def _opt(cls, v):
+        return None if v == cls.NONE else v
+
+    @classmethod
+    def _filled(cls, fn: str, *args):
+        """The result that the libdse call ``fn(*args, out)`` writes; a uint64 array
+        among args goes as the pointer to its words, an empty one as None."""
+        out = np.zeros(cls.WORDS, dtype=np.uint64)
+        ptrs = [(u64p(a) if len(a) else None) if isinstance(a, np.ndarray) else a for a in args]
+        check(getattr(lib(), fn)(*ptrs, u64p(out)), fn)
+        return cls(out)
+
+    def merge(self, other):
+        """The result of this range followed by the adjacent ``other`` (dse_<unit>_merge;
+        a Race's ``other`` started from this one's d_end)."""
+        return self._filled("dse_%s_merge" % self.UNIT, self.words, other.words)
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and np.array_equal(self.words, other.words)
+
+
+def _words(bits):
+    """A host mask (or ``above`` / ``below``, which may be None) as contiguous uint64 words."""
+    return None if bits is None else np.ascontiguousarray(bits, dtype=np.uint64)
+
+
+class Stats(_Result):
     """One dse_stats (include/dse.h): the constellation counts and gap statistics
     of the odd candidates [g_start, g_start + nbits). ``words`` is the struct as
     its uint64 words."""
 
-    def __init__(self, words: np.ndarray):
-        w = np.ascontiguousarray(words, dtype=np.uint64)
-        if w.shape != (_dse.STATS_WORDS,):
-            raise ValueError("a dse_stats is %d uint64 words" % _dse.STATS_WORDS)
-        self.words = w
-
-    @staticmethod
-    def _opt(v):
-        return None if v == _dse.STATS_NONE else v
+    UNIT, WORDS, NONE = "stats", _dse.STATS_WORDS, _dse.STATS_NONE
 
     g_start = property(lambda s: int(s.words[0]))
     nbits = property(lambda s: int(s.words[1]))
     primes = property(lambda s: int(s.words[2]))
-    first_g = property(lambda s: Stats._opt(int(s.words[3])))
-    last_g = property(lambda s: Stats._opt(int(s.words[4])))
+    first_g = property(lambda s: s._opt(int(s.words[3])))
+    last_g = property(lambda s: s._opt(int(s.words[4])))
     head = property(lambda s: int(s.words[5]))
     tail = property(lambda s: int(s.words[6]))
     gap_overflow = property(lambda s: int(s.words[26]))
     max_gap = property(lambda s: int(s.words[24]))
-    max_gap_g = property(lambda s: Stats._opt(int(s.words[25])))
+    max_gap_g = property(lambda s: s._opt(int(s.words[25])))
 
     @property
     def first(self) -> Optional[int]:
@@ -146,15 +180,6 @@ class Stats:
         """The lower prime of the first maximal gap, or None with fewer than two primes."""
         return None if self.max_gap_g is None else 3 + 2 * self.max_gap_g
 
-    def merge(self, other: "Stats") -> "Stats":
-        """The statistics of this range followed by the adjacent ``other`` (dse_stats_merge)."""
-        out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
-        check(lib().dse_stats_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_stats_merge")
-        return Stats(out)
-
-    def __eq__(self, other):
-        return isinstance(other, Stats) and np.array_equal(self.words, other.words)
-
     def __repr__(self):
         return (f"Stats(g_start={self.g_start}, nbits={self.nbits}, primes={self.primes}, matches={self.matches}, "
                 f"max_gap={self.max_gap} at {self.max_gap_prime})")
@@ -164,37 +189,25 @@ def stats_host(mask: np.ndarray, g_start: int, nbits: int, patterns=CONSTELLATIO
     """Test-only: the statistics kernels' per-word bodies run on the host over a
     host mask (include/dse.h dse_debug_stats_host)."""
     pats, n = _patterns(patterns)
-    out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
-    m = np.ascontiguousarray(mask, dtype=np.uint64)
-    check(lib().dse_debug_stats_host(u64p(m) if len(m) else None, g_start, nbits, pats, n, u64p(out)),
-          "dse_debug_stats_host")
-    return Stats(out)
+    return Stats._filled("dse_debug_stats_host", _words(mask), g_start, nbits, pats, n)
 
 
-class Gaps:
+class Gaps(_Result):
     """One dse_gaps (include/dse.h "where the gaps are"): the first occurrence of
     every prime gap of the odd candidates [g_start, g_start + nbits). ``words`` is
     the struct as its uint64 words."""
 
-    def __init__(self, words: np.ndarray):
-        w = np.ascontiguousarray(words, dtype=np.uint64)
-        if w.shape != (_dse.GAPS_WORDS,):
-            raise ValueError("a dse_gaps is %d uint64 words" % _dse.GAPS_WORDS)
-        self.words = w
-
-    @staticmethod
-    def _opt(v):
-        return None if v == _dse.GAPS_NONE else v
+    UNIT, WORDS, NONE = "gaps", _dse.GAPS_WORDS, _dse.GAPS_NONE
 
     g_start = property(lambda s: int(s.words[0]))
     nbits = property(lambda s: int(s.words[1]))
     primes = property(lambda s: int(s.words[2]))
-    first_g = property(lambda s: Gaps._opt(int(s.words[3])))
-    last_g = property(lambda s: Gaps._opt(int(s.words[4])))
+    first_g = property(lambda s: s._opt(int(s.words[3])))
+    last_g = property(lambda s: s._opt(int(s.words[4])))
     found = property(lambda s: int(s.words[5]))
     max_gap = property(lambda s: int(s.words[6]))
-    max_gap_g = property(lambda s: Gaps._opt(int(s.words[7])))
-    overflow_g = property(lambda s: Gaps._opt(int(s.words[8])))
+    max_gap_g = property(lambda s: s._opt(int(s.words[7])))
+    overflow_g = property(lambda s: s._opt(int(s.words[8])))
 
     @property
     def first(self) -> np.ndarray:
@@ -223,15 +236,6 @@ class Gaps:
         check(lib().dse_gaps_records(u64p(self.words), d, _dse.GAPS_BINS, ctypes.byref(n)), "dse_gaps_records")
         return self._pairs(d[:n.value])
 
-    def merge(self, other: "Gaps") -> "Gaps":
-        """The table of this range followed by the adjacent ``other`` (dse_gaps_merge)."""
-        out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
-        check(lib().dse_gaps_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_gaps_merge")
-        return Gaps(out)
-
-    def __eq__(self, other):
-        return isinstance(other, Gaps) and np.array_equal(self.words, other.words)
-
     def __repr__(self):
         return (f"Gaps(g_start={self.g_start}, nbits={self.nbits}, primes={self.primes}, found={self.found}, "
                 f"max_gap={self.max_gap} at {self.max_gap_prime})")
@@ -240,35 +244,24 @@ class Gaps:
 def gaps_host(mask: np.ndarray, g_start: int, nbits: int) -> Gaps:
     """Test-only: the gaps kernels' per-word bodies run on the host over a host mask
     (include/dse.h dse_debug_gaps_host)."""
-    out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
-    m = np.ascontiguousarray(mask, dtype=np.uint64)
-    check(lib().dse_debug_gaps_host(u64p(m) if len(m) else None, g_start, nbits, u64p(out)), "dse_debug_gaps_host")
-    return Gaps(out)
+    return Gaps._filled("dse_debug_gaps_host", _words(mask), g_start, nbits)
 
 
-class Consec:
+class Consec(_Result):
     """One dse_consec (include/dse.h "residue pairs of consecutive primes"): for the
     modulus q the pairs of consecutive primes of the odd candidates [g_start, g_start
     + nbits) by the classes of the lower and the upper prime. ``words`` is the struct
     as its uint64 words."""
 
-    def __init__(self, words: np.ndarray):
-        w = np.ascontiguousarray(words, dtype=np.uint64)
-        if w.shape != (_dse.CONSEC_WORDS,):
-            raise ValueError("a dse_consec is %d uint64 words" % _dse.CONSEC_WORDS)
-        self.words = w
-
-    @staticmethod
-    def _opt(v):
-        return None if v == _dse.CONSEC_NONE else v
+    UNIT, WORDS, NONE = "consec", _dse.CONSEC_WORDS, _dse.CONSEC_NONE
 
     g_start = property(lambda s: int(s.words[0]))
     nbits = property(lambda s: int(s.words[1]))
     q = property(lambda s: int(s.words[2]))
     primes = property(lambda s: int(s.words[3]))
     pairs = property(lambda s: int(s.words[4]))
-    first_g = property(lambda s: Consec._opt(int(s.words[5])))
-    last_g = property(lambda s: Consec._opt(int(s.words[6])))
+    first_g = property(lambda s: s._opt(int(s.words[5])))
+    last_g = property(lambda s: s._opt(int(s.words[6])))
 
     @property
     def counts(self) -> np.ndarray:
@@ -281,15 +274,6 @@ class Consec:
         and p' = b (mod q)."""
         return self.counts[:self.q, :self.q]
 
-    def merge(self, other: "Consec") -> "Consec":
-        """The matrix of this range followed by the adjacent ``other`` (dse_consec_merge)."""
-        out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
-        check(lib().dse_consec_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_consec_merge")
-        return Consec(out)
-
-    def __eq__(self, other):
-        return isinstance(other, Consec) and np.array_equal(self.words, other.words)
-
     def __repr__(self):
         return (f"Consec(g_start={self.g_start}, nbits={self.nbits}, q={self.q}, primes={self.primes}, "
                 f"pairs={self.pairs})")
@@ -298,28 +282,16 @@ class Consec:
 def consec_host(mask: np.ndarray, g_start: int, nbits: int, q: int) -> Consec:
     """Test-only: the consec kernels' per-word bodies run on the host over a host mask
     (include/dse.h dse_debug_consec_host)."""
-    out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
-    m = np.ascontiguousarray(mask, dtype=np.uint64)
-    check(lib().dse_debug_consec_host(u64p(m) if len(m) else None, g_start, nbits, q, u64p(out)),
-          "dse_debug_consec_host")
-    return Consec(out)
+    return Consec._filled("dse_debug_consec_host", _words(mask), g_start, nbits, q)
 
 
-class Sums:
+class Sums(_Result):
     """One dse_sums (include/dse.h "power and reciprocal sums"): the matches of a
     pattern in the odd candidates [g_start, g_start + nbits), the sum of their values
     and of the squares, and the fixed-point sum of the reciprocals of their required
     members, all exact integers. ``words`` is the struct as its uint64 words."""
 
-    def __init__(self, words: np.ndarray):
-        w = np.ascontiguousarray(words, dtype=np.uint64)
-        if w.shape != (_dse.SUMS_WORDS,):
-            raise ValueError("a dse_sums is %d uint64 words" % _dse.SUMS_WORDS)
-        self.words = w
-
-    @staticmethod
-    def _opt(v):
-        return None if v == _dse.SUMS_NONE else v
+    UNIT, WORDS, NONE = "sums", _dse.SUMS_WORDS, _dse.SUMS_NONE
 
     def _limbs(self, at: int, n: int) -> int:
         return sum(int(self.words[at + k]) << (64 * k) for k in range(n))
@@ -331,8 +303,8 @@ class Sums:
     above_bits = property(lambda s: int(s.words[4]))
     flags = property(lambda s: int(s.words[5]))
     matches = property(lambda s: int(s.words[6]))
-    first_g = property(lambda s: Sums._opt(int(s.words[7])))
-    last_g = property(lambda s: Sums._opt(int(s.words[8])))
+    first_g = property(lambda s: s._opt(int(s.words[7])))
+    last_g = property(lambda s: s._opt(int(s.words[8])))
     sum1 = property(lambda s: s._limbs(9, 2), doc="the sum of the matches' values (0 without SUMS_POWER)")
     sum2 = property(lambda s: s._limbs(11, 3), doc="the sum of their squares (0 without SUMS_POWER)")
     recip = property(lambda s: s._limbs(14, 3),
@@ -360,15 +332,6 @@ class Sums:
         """The sum of the reciprocals as a float (the lower bound, rounded)."""
         return self.recip / (1 << _dse.SUMS_RECIP_SHIFT)
 
-    def merge(self, other: "Sums") -> "Sums":
-        """The sums of this range followed by the adjacent ``other`` (dse_sums_merge)."""
-        out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
-        check(lib().dse_sums_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_sums_merge")
-        return Sums(out)
-
-    def __eq__(self, other):
-        return isinstance(other, Sums) and np.array_equal(self.words, other.words)
-
     def __repr__(self):
         return (f"Sums(g_start={self.g_start}, nbits={self.nbits}, require={self.require:#x}, forbid={self.forbid:#x}, "
                 f"flags={self.flags}, matches={self.matches}, sum1={self.sum1}, sum2={self.sum2}, "
@@ -380,13 +343,8 @@ def sums_host(mask: np.ndarray, g_start: int, nbits: int, require: int = 1, forb
               flags: int = _dse.SUMS_POWER | _dse.SUMS_RECIP) -> Sums:
     """Test-only: the sums kernels' per-word and per-entry bodies run on the host over
     a host mask and a host ``above`` (include/dse.h dse_debug_sums_host)."""
-    out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
-    m = np.ascontiguousarray(mask, dtype=np.uint64)
-    a = None if above is None else np.ascontiguousarray(above, dtype=np.uint64)
-    check(lib().dse_debug_sums_host(u64p(m) if len(m) else None, g_start, nbits, require, forbid,
-                                    u64p(a) if a is not None and len(a) else None, above_shift, above_bits, flags,
-                                    u64p(out)), "dse_debug_sums_host")
-    return Sums(out)
+    return Sums._filled("dse_debug_sums_host", _words(mask), g_start, nbits, require, forbid,
+                        _words(above), above_shift, above_bits, flags)
 
 
 def sums_recip_host(values) -> List[int]:
@@ -400,29 +358,21 @@ def sums_recip_host(values) -> List[int]:
     return [l | h << 64 for l, h in zip(lo, hi)]
 
 
-class Goldbach:
+class Goldbach(_Result):
     """One dse_goldbach (include/dse.h "additive questions"): the minimal Goldbach
     partitions of the evens 6 + 2c of the odd candidates [g_start, g_start +
     nbits). ``words`` is the struct as its uint64 words."""
 
-    def __init__(self, words: np.ndarray):
-        w = np.ascontiguousarray(words, dtype=np.uint64)
-        if w.shape != (_dse.GOLDBACH_WORDS,):
-            raise ValueError("a dse_goldbach is %d uint64 words" % _dse.GOLDBACH_WORDS)
-        self.words = w
-
-    @staticmethod
-    def _opt(v):
-        return None if v == _dse.GOLDBACH_NONE else v
+    UNIT, WORDS, NONE = "goldbach", _dse.GOLDBACH_WORDS, _dse.GOLDBACH_NONE
 
     g_start = property(lambda s: int(s.words[0]))
     nbits = property(lambda s: int(s.words[1]))
     nprimes = property(lambda s: int(s.words[2]))
     resolved = property(lambda s: int(s.words[3]))
     unresolved = property(lambda s: int(s.words[4]))
-    first_unresolved = property(lambda s: Goldbach._opt(int(s.words[5])))
-    max_rank = property(lambda s: Goldbach._opt(int(s.words[6])))
-    max_c = property(lambda s: Goldbach._opt(int(s.words[7])))
+    first_unresolved = property(lambda s: s._opt(int(s.words[5])))
+    max_rank = property(lambda s: s._opt(int(s.words[6])))
+    max_c = property(lambda s: s._opt(int(s.words[7])))
 
     @property
     def hist(self) -> np.ndarray:
@@ -444,15 +394,6 @@ class Goldbach:
         """The first even whose minimal prime is ``max_prime``, or None."""
         return None if self.max_c is None else 6 + 2 * self.max_c
 
-    def merge(self, other: "Goldbach") -> "Goldbach":
-        """The result of this range followed by the adjacent ``other`` (dse_goldbach_merge)."""
-        out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
-        check(lib().dse_goldbach_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_goldbach_merge")
-        return Goldbach(out)
-
-    def __eq__(self, other):
-        return isinstance(other, Goldbach) and np.array_equal(self.words, other.words)
-
     def __repr__(self):
         return (f"Goldbach(g_start={self.g_start}, nbits={self.nbits}, nprimes={self.nprimes}, "
                 f"unresolved={self.unresolved}, max_prime={self.max_prime} at {self.max_even})")
@@ -462,25 +403,16 @@ def goldbach_host(mask: np.ndarray, g_start: int, nbits: int, below: Optional[np
                   below_shift: int = 0, below_bits: int = 0, nprimes: int = 0) -> Goldbach:
     """Test-only: the Goldbach kernel's per-word bodies run on the host over a host
     mask and a host ``below`` (include/dse.h dse_debug_goldbach_host)."""
-    out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
-    m = np.ascontiguousarray(mask, dtype=np.uint64)
-    b = None if below is None else np.ascontiguousarray(below, dtype=np.uint64)
-    check(lib().dse_debug_goldbach_host(u64p(m) if len(m) else None, g_start, nbits,
-                                        u64p(b) if b is not None and len(b) else None, below_shift, below_bits,
-                                        nprimes, u64p(out)), "dse_debug_goldbach_host")
-    return Goldbach(out)
+    return Goldbach._filled("dse_debug_goldbach_host", _words(mask), g_start, nbits,
+                            _words(below), below_shift, below_bits, nprimes)
 
 
-class Race:
+class Race(_Result):
     """One dse_race (include/dse.h "residue classes and races"): the entries of the
     odd candidates [g_start, g_start + nbits) per class mod q, and the race of class
     a against class b from d_start. ``words`` is the struct as its uint64 words."""
 
-    def __init__(self, words: np.ndarray):
-        w = np.ascontiguousarray(words, dtype=np.uint64)
-        if w.shape != (_dse.RACE_WORDS,):
-            raise ValueError("a dse_race is %d uint64 words" % _dse.RACE_WORDS)
-        self.words = w
+    UNIT, WORDS, NONE = "race", _dse.RACE_WORDS, _dse.RACE_NONE
 
     def _signed(self, i):
         v = int(self.words[i])
@@ -513,16 +445,6 @@ class Race:
         """uint64[q]: counts[r] = entries whose value is r mod q."""
         return self.words[17:17 + self.q]
 
-    def merge(self, other: "Race") -> "Race":
-        """The result of this range followed by the adjacent ``other``, which started
-        from this one's d_end (dse_race_merge)."""
-        out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
-        check(lib().dse_race_merge(u64p(self.words), u64p(other.words), u64p(out)), "dse_race_merge")
-        return Race(out)
-
-    def __eq__(self, other):
-        return isinstance(other, Race) and np.array_equal(self.words, other.words)
-
     def __repr__(self):
         return (f"Race(g_start={self.g_start}, nbits={self.nbits}, q={self.q}, a={self.a}, b={self.b}, "
                 f"d_start={self.d_start}, d_end={self.d_end}, steps={self.steps}, a_ahead={self.a_ahead}, "
@@ -534,11 +456,7 @@ class Race:
 def race_host(mask: np.ndarray, g_start: int, nbits: int, q: int, a: int, b: int, d_start: int = 0) -> Race:
     """Test-only: the race kernels' per-word bodies run on the host over a host mask
     (include/dse.h dse_debug_race_host)."""
-    out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
-    m = np.ascontiguousarray(mask, dtype=np.uint64)
-    check(lib().dse_debug_race_host(u64p(m) if len(m) else None, g_start, nbits, q, a, b, d_start, u64p(out)),
-          "dse_debug_race_host")
-    return Race(out)
+    return Race._filled("dse_debug_race_host", _words(mask), g_start, nbits, q, a, b, d_start)
 
 
 class Context:
@@ -721,11 +639,24 @@ class Context:
     def primes_window(self, lo: int, hi: int) -> np.ndarray:
         """The odd primes in [max(lo, 3), hi] (sieve_window's convention: its
         count is this array's length)."""
-        a = max(lo, 3) | 1
-        if hi < a:
-            return np.empty(0, dtype=np.uint64)
-        b = hi if hi & 1 else hi - 1
-        return self.primes_range((a - 3) // 2, (b - a) // 2 + 1)
+        g, n = self._window(lo, hi)
+        return self.primes_range(g, n) if n else np.empty(0, dtype=np.uint64)
+
+    # -- what the slab units' methods share -----------------------------------------
+    def _result(self, cls, fn: str, *args):
+        """The ``cls`` that the libdse call ``fn(ctx, *args, out)`` fills."""
+        return cls._filled(fn, self.ptr, *args)
+
+    @staticmethod
+    def _window(lo: int, hi: int, base: int = 3):
+        """-> (g_start, nbits) of the values of base's parity in [max(lo, base), hi],
+        g counting them from base; an empty window is (min(g_start, 2^62), 0)."""
+        a = max(lo, base)
+        a += (a ^ base) & 1
+        b = hi - ((hi ^ base) & 1)
+        if b < a:
+            return min((a - base) // 2, 1 << 62), 0
+        return (a - base) // 2, (b - a) // 2 + 1
 
     # -- statistics of a mask -----------------------------------------------------
     def stats_dev_async(self, g_start: int, nbits: int, mask_ptr: int, patterns, stats_ptr: int,
@@ -741,28 +672,17 @@ class Context:
     def stats_range(self, g_start: int, nbits: int, patterns=CONSTELLATIONS) -> Stats:
         """gen-table + sieve-e of an odd-index range and its statistics, computed
         on the device: only the dse_stats reaches the host."""
-        pats, n = _patterns(patterns)
-        out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
-        check(lib().dse_stats_range(self.ptr, g_start, nbits, pats, n, u64p(out)), "dse_stats_range")
-        return Stats(out)
+        return self._result(Stats, "dse_stats_range", g_start, nbits, *_patterns(patterns))
 
     def resident_stats(self, my_num: Optional[int] = None, patterns=CONSTELLATIONS) -> Stats:
         """The statistics of a chunk the last sieve_all left on its device, or
         (my_num=None) of all its chunks: the per-chunk results merged in order."""
-        pats, n = _patterns(patterns)
-        out = np.zeros(_dse.STATS_WORDS, dtype=np.uint64)
-        check(lib().dse_stats_resident(self.ptr, 0 if my_num is None else my_num, pats, n, u64p(out)),
-              "dse_stats_resident")
-        return Stats(out)
+        return self._result(Stats, "dse_stats_resident", my_num or 0, *_patterns(patterns))
 
     def stats_window(self, lo: int, hi: int, patterns=CONSTELLATIONS) -> Stats:
         """The statistics of the odd values in [max(lo, 3), hi] (primes_window's
         convention); an empty window gives the empty result."""
-        a = max(lo, 3) | 1
-        if hi < a:
-            return self.stats_range(min((a - 3) // 2, 1 << 62), 0, patterns)
-        b = hi if hi & 1 else hi - 1
-        return self.stats_range((a - 3) // 2, (b - a) // 2 + 1, patterns)
+        return self.stats_range(*self._window(lo, hi), patterns)
 
     # -- where the gaps are -----------------------------------------------------------
     def gaps_dev_async(self, g_start: int, nbits: int, mask_ptr: int, out_ptr: int, stream_ptr: int = 0):
@@ -776,25 +696,17 @@ class Context:
     def gaps_range(self, g_start: int, nbits: int) -> Gaps:
         """gen-table + sieve-e of an odd-index range and the first occurrence of every
         gap in it, computed on the device: only the dse_gaps reaches the host."""
-        out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
-        check(lib().dse_gaps_range(self.ptr, g_start, nbits, u64p(out)), "dse_gaps_range")
-        return Gaps(out)
+        return self._result(Gaps, "dse_gaps_range", g_start, nbits)
 
     def resident_gaps(self, my_num: Optional[int] = None) -> Gaps:
         """The table of a chunk the last sieve_all left on its device, or (my_num=None)
         of all its chunks: the per-chunk results merged in order."""
-        out = np.zeros(_dse.GAPS_WORDS, dtype=np.uint64)
-        check(lib().dse_gaps_resident(self.ptr, 0 if my_num is None else my_num, u64p(out)), "dse_gaps_resident")
-        return Gaps(out)
+        return self._result(Gaps, "dse_gaps_resident", my_num or 0)
 
     def gaps_window(self, lo: int, hi: int) -> Gaps:
         """The table of the odd values in [max(lo, 3), hi] (primes_window's convention);
         an empty window gives the empty result."""
-        a = max(lo, 3) | 1
-        if hi < a:
-            return self.gaps_range(min((a - 3) // 2, 1 << 62), 0)
-        b = hi if hi & 1 else hi - 1
-        return self.gaps_range((a - 3) // 2, (b - a) // 2 + 1)
+        return self.gaps_range(*self._window(lo, hi))
 
     # -- residue pairs of consecutive primes ------------------------------------------
     def consec_dev_async(self, g_start: int, nbits: int, mask_ptr: int, q: int, out_ptr: int, stream_ptr: int = 0):
@@ -809,26 +721,17 @@ class Context:
         """gen-table + sieve-e of an odd-index range and the pairs of its consecutive
         primes by their classes mod q, computed on the device: only the dse_consec
         reaches the host."""
-        out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
-        check(lib().dse_consec_range(self.ptr, g_start, nbits, q, u64p(out)), "dse_consec_range")
-        return Consec(out)
+        return self._result(Consec, "dse_consec_range", g_start, nbits, q)
 
     def resident_consec(self, my_num: Optional[int] = None, q: int = 10) -> Consec:
         """The matrix of a chunk the last sieve_all left on its device, or (my_num=None)
         of all its chunks: the per-chunk results merged in order."""
-        out = np.zeros(_dse.CONSEC_WORDS, dtype=np.uint64)
-        check(lib().dse_consec_resident(self.ptr, 0 if my_num is None else my_num, q, u64p(out)),
-              "dse_consec_resident")
-        return Consec(out)
+        return self._result(Consec, "dse_consec_resident", my_num or 0, q)
 
     def consec_window(self, lo: int, hi: int, q: int) -> Consec:
         """The matrix of the odd values in [max(lo, 3), hi] (primes_window's convention);
         an empty window gives the empty result."""
-        a = max(lo, 3) | 1
-        if hi < a:
-            return self.consec_range(min((a - 3) // 2, 1 << 62), 0, q)
-        b = hi if hi & 1 else hi - 1
-        return self.consec_range((a - 3) // 2, (b - a) // 2 + 1, q)
+        return self.consec_range(*self._window(lo, hi), q)
 
     # -- power and reciprocal sums ----------------------------------------------------
     def sums_dev_async(self, g_start: int, nbits: int, mask_ptr: int, require: int, forbid: int, above_ptr: int,
@@ -847,29 +750,20 @@ class Context:
         """gen-table + sieve-e of an odd-index range (and of the 31 candidates above
         it) and the sums over its matches of (require, forbid), computed on the
         device: only the dse_sums reaches the host."""
-        out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
-        check(lib().dse_sums_range(self.ptr, g_start, nbits, require, forbid, flags, u64p(out)), "dse_sums_range")
-        return Sums(out)
+        return self._result(Sums, "dse_sums_range", g_start, nbits, require, forbid, flags)
 
     def sums_resident(self, my_num: Optional[int] = None, require: int = 1, forbid: int = 0,
                       flags: int = _dse.SUMS_POWER | _dse.SUMS_RECIP) -> Sums:
         """The sums of a chunk the last sieve_all left on its device, or (my_num=None)
         of all its chunks: the per-chunk results merged in order."""
-        out = np.zeros(_dse.SUMS_WORDS, dtype=np.uint64)
-        check(lib().dse_sums_resident(self.ptr, 0 if my_num is None else my_num, require, forbid, flags, u64p(out)),
-              "dse_sums_resident")
-        return Sums(out)
+        return self._result(Sums, "dse_sums_resident", my_num or 0, require, forbid, flags)
 
     def sums_window(self, lo: int, hi: int, require: int = 1, forbid: int = 0,
                     flags: int = _dse.SUMS_POWER | _dse.SUMS_RECIP) -> Sums:
         """The sums over the matches whose lowest member is an odd value in
         [max(lo, 3), hi] (primes_window's convention); an empty window gives the
         empty result."""
-        a = max(lo, 3) | 1
-        if hi < a:
-            return self.sums_range(min((a - 3) // 2, 1 << 62), 0, require, forbid, flags)
-        b = hi if hi & 1 else hi - 1
-        return self.sums_range((a - 3) // 2, (b - a) // 2 + 1, require, forbid, flags)
+        return self.sums_range(*self._window(lo, hi), require, forbid, flags)
 
     # -- constellations as numbers -------------------------------------------------
     def tuples_dev_async(self, g_start: int, nbits: int, mask_ptr: int, require: int, forbid: int, above_ptr: int,
@@ -909,11 +803,8 @@ class Context:
     def tuples_window(self, lo: int, hi: int, require: int, forbid: int = 0) -> np.ndarray:
         """The matches whose lowest member lies in the odd values of [max(lo, 3), hi]
         (primes_window's convention); the other members may lie above hi."""
-        a = max(lo, 3) | 1
-        if hi < a:
-            return np.empty(0, dtype=np.uint64)
-        b = hi if hi & 1 else hi - 1
-        return self.tuples_range((a - 3) // 2, (b - a) // 2 + 1, require, forbid)
+        g, n = self._window(lo, hi)
+        return self.tuples_range(g, n, require, forbid) if n else np.empty(0, dtype=np.uint64)
 
 
     # -- additive questions -------------------------------------------------------
@@ -931,28 +822,18 @@ class Context:
         """gen-table + sieve-e of an odd-index range (and of what the small primes
         reach below it) and the minimal Goldbach partitions of its evens 6 + 2c,
         computed on the device: only the dse_goldbach reaches the host."""
-        out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
-        check(lib().dse_goldbach_range(self.ptr, g_start, nbits, nprimes, u64p(out)), "dse_goldbach_range")
-        return Goldbach(out)
+        return self._result(Goldbach, "dse_goldbach_range", g_start, nbits, nprimes)
 
     def goldbach_window(self, lo: int, hi: int, nprimes: int = 0) -> Goldbach:
         """The minimal Goldbach partitions of the evens in [max(lo, 6), hi]; an
         empty window gives the empty result."""
-        a = max(lo, 6)
-        a += a & 1
-        b = hi - (hi & 1)
-        if b < a:
-            return self.goldbach_range(min((a - 6) // 2, 1 << 62), 0, nprimes)
-        return self.goldbach_range((a - 6) // 2, (b - a) // 2 + 1, nprimes)
+        return self.goldbach_range(*self._window(lo, hi, base=6), nprimes)
 
     def resident_goldbach(self, my_num: Optional[int] = None, nprimes: int = 0) -> Goldbach:
         """The minimal Goldbach partitions of a chunk the last sieve_all left on
         its device (it sees the tail of the chunk before it), or (my_num=None) of
         all its chunks: the per-chunk results merged in order."""
-        out = np.zeros(_dse.GOLDBACH_WORDS, dtype=np.uint64)
-        check(lib().dse_goldbach_resident(self.ptr, 0 if my_num is None else my_num, nprimes, u64p(out)),
-              "dse_goldbach_resident")
-        return Goldbach(out)
+        return self._result(Goldbach, "dse_goldbach_resident", my_num or 0, nprimes)
 
     # -- residue classes and races -------------------------------------------------
     def race_dev_async(self, g_start: int, nbits: int, mask_ptr: int, q: int, a: int, b: int, d_start: int,
@@ -966,28 +847,19 @@ class Context:
     def race_range(self, g_start: int, nbits: int, q: int, a: int, b: int, d_start: int = 0) -> Race:
         """gen-table + sieve-e of an odd-index range and its class counts and race,
         computed on the device: only the dse_race reaches the host."""
-        out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
-        check(lib().dse_race_range(self.ptr, g_start, nbits, q, a, b, d_start, u64p(out)), "dse_race_range")
-        return Race(out)
+        return self._result(Race, "dse_race_range", g_start, nbits, q, a, b, d_start)
 
     def race_window(self, lo: int, hi: int, q: int, a: int, b: int, d_start: int = 0) -> Race:
         """The class counts and race of the odd values in [max(lo, 3), hi]
         (primes_window's convention); an empty window gives the empty result."""
-        x = max(lo, 3) | 1
-        if hi < x:
-            return self.race_range(min((x - 3) // 2, 1 << 62), 0, q, a, b, d_start)
-        y = hi if hi & 1 else hi - 1
-        return self.race_range((x - 3) // 2, (y - x) // 2 + 1, q, a, b, d_start)
+        return self.race_range(*self._window(lo, hi), q, a, b, d_start)
 
     def resident_race(self, my_num: Optional[int] = None, q: int = 4, a: int = 1, b: int = 3,
                       d_start: int = 0) -> Race:
         """The class counts and race of a chunk the last sieve_all left on its
         device, or (my_num=None) of all its chunks as one range: every chunk starts
         from the d_end of the one before it, and the results are merged in order."""
-        out = np.zeros(_dse.RACE_WORDS, dtype=np.uint64)
-        check(lib().dse_race_resident(self.ptr, 0 if my_num is None else my_num, q, a, b, d_start, u64p(out)),
-              "dse_race_resident")
-        return Race(out)
+        return self._result(Race, "dse_race_resident", my_num or 0, q, a, b, d_start)
 
     # -- rank and select ---------------------------------------------------------
     def query_index_dev_async(self, g_start: int, nbits: int, mask_ptr: int, index_ptr: int, index_bytes: int,

@@ -501,6 +501,8 @@ def test_debug_numeric_options_refuse_out_of_range(oracle):
            ("bucket_k0_divisor", u32), ("scratch_poison", -1), ("scratch_poison", 2),
            ("table_broadcast_max_bytes", -1), ("finish_slab_words", -1), ("bucket_cap_divisor", -1),
            ("bucket_cap_divisor", u32), ("bucket_lo_log2", 16), ("bucket_lo_log2", wheel_max_log + 1)]
+    for unit in ("stats", "goldbach", "race", "gaps", "sums", "consec"):  # each unit's maximum is 1024 (dse_internal.h)
+        bad += [(unit + "_grid", -1), (unit + "_grid", 1025)]
     N, P = 10**6, 3
     _, m_ref, c_ref, _ = oracle.sieve(N, P)
     for logical in (None, 2):
@@ -514,6 +516,40 @@ def test_debug_numeric_options_refuse_out_of_range(oracle):
             assert [int(x) for x in counts] == [int(x) for x in c_ref]
             for k in range(1, P + 1):
                 assert np.array_equal(c.copy_chunk_mask(N, P, k), m_ref[k - 1]), k
+
+
+def test_unit_grid_options_reach_their_units():
+    """Every "<unit>_grid" option caps the launches of its own unit: with the grid at 1 (one
+    workgroup walks every tile) and at 1024 (more workgroups than tiles) the unit's *_range over
+    three tiles and a partial one equals its *_host over a mask sieved on the CPU."""
+    from mail_sieve_e import sieve as S
+    nbits = 3 * 16384 + 37
+    top = 3 + 2 * (nbits + 31)  # sums sees 31 candidates above the range
+    is_p = np.ones(top, dtype=bool)
+    is_p[:2] = False
+    for p in range(2, int(top ** 0.5) + 1):
+        if is_p[p]:
+            is_p[p * p::p] = False
+    bits = np.zeros((nbits + 31 + 63) // 64 * 64, dtype=np.uint8)
+    bits[:nbits + 31] = is_p[3::2][:nbits + 31]
+    mask = np.packbits(bits, bitorder="little").view(np.uint64)
+    units = {
+        "stats": (lambda c: c.stats_range(0, nbits), lambda: S.stats_host(mask, 0, nbits)),
+        "goldbach": (lambda c: c.goldbach_range(0, nbits), lambda: S.goldbach_host(mask, 0, nbits)),
+        "race": (lambda c: c.race_range(0, nbits, 4, 1, 3), lambda: S.race_host(mask, 0, nbits, 4, 1, 3)),
+        "gaps": (lambda c: c.gaps_range(0, nbits), lambda: S.gaps_host(mask, 0, nbits)),
+        "sums": (lambda c: c.sums_range(0, nbits),
+                 lambda: S.sums_host(mask, 0, nbits, above=mask[nbits // 64:], above_shift=nbits % 64, above_bits=31)),
+        "consec": (lambda c: c.consec_range(0, nbits, 10), lambda: S.consec_host(mask, 0, nbits, 10)),
+    }
+    with S.Context(num_gpus=1) as c:
+        for unit, (on_device, on_host) in units.items():
+            want = on_host()
+            assert want.nbits == nbits, unit
+            for grid in (1, 1024):
+                c.debug_set_option(unit + "_grid", grid)
+                assert on_device(c) == want, (unit, grid)
+            c.debug_set_option(unit + "_grid", 0)
 
 
 @pytest.mark.parametrize("logical", [None, 2])
